@@ -20,6 +20,11 @@ Launch (driver contract):
   python bench.py --gpus 1 --steps 30 --warmup 5
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR also writes what the last timed step returned (see
+dump_outputs); --full is reserved for secondary measurements that need runs
+of their own (none today: every reported figure comes from the timed steps).
 """
 import argparse
 import json
@@ -115,6 +120,43 @@ def partition_cpus(world, rank):
     return my, ens, effective
 
 
+def dump_outputs(out_dir, last, rank, world):
+    """Write what the last timed step handed back to its caller as
+    out_dir/<name>.npy, so two builds can be compared output for output.
+
+    The step's inputs (the registration config) are a pure function of the
+    command-line arguments and the rank, so with the same arguments these
+    arrays are identical from run to run:
+      register_rc   float64 [1]     register_()'s return code
+      znodes        float32 [n, w]  the znode paths register_() returned, in
+                                    the order returned: row i holds the UTF-8
+                                    bytes of path i, zero-padded to width w
+      heartbeat_rc  float64 [1]     heartbeat()'s return code
+    The heartbeat's measured RTT is a timing, not a computed value, and is
+    reported in the result line instead. With several ranks each rank writes
+    its own files, suffixed _rank<r>."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    paths = [p.encode("utf-8") for p in last["znodes"]]
+    width = max([len(p) for p in paths] + [1])
+    max_rows = (60 << 20) // (4 * width)  # keep the dump under 64 MB
+    if len(paths) > max_rows:  # a fixed, seeded sample of the rows, in order
+        keep = np.sort(np.random.default_rng(0).choice(len(paths), max_rows, replace=False))
+        paths = [paths[i] for i in keep]
+    table = np.zeros((len(paths), width), dtype=np.float32)
+    for i, p in enumerate(paths):
+        table[i, :len(p)] = np.frombuffer(p, dtype=np.uint8)
+    arrays = {
+        "register_rc": np.array([last["register_rc"]], dtype=np.float64),
+        "znodes": table,
+        "heartbeat_rc": np.array([last["heartbeat_rc"]], dtype=np.float64),
+    }
+    suffix = "" if world == 1 else "_rank%d" % rank
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -125,7 +167,17 @@ def main():
                     help="ensemble server count (0 = auto: 1 for a single proc, "
                          "3 — the standard ZK quorum size — for multi-proc, "
                          "matching BASELINE configs 1 vs 2/3)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step "
+                         "returned to its caller as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the benchmark's secondary measurements; a plain "
+                         "run does only what the headline figure needs (today every "
+                         "figure in the result line comes from the timed steps "
+                         "themselves, so --full adds no work)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # The driver contract is ONE JSON line on stdout from rank 0 — but gloo
     # writes "[Gloo] Rank ... connected ..." banners straight to fd 1 via
@@ -245,6 +297,7 @@ def main():
     prep = ra.PreparedRegistration(json.dumps(registration))
 
     phase_time = {"reg": 0.0, "hb": 0.0}
+    last = {}  # what the most recent step returned (for --dump-outputs)
 
     def step():
         """One full re-register of all znodes + one 1k-node heartbeat."""
@@ -253,11 +306,13 @@ def main():
         t1 = time.perf_counter()
         if rc != 0:
             raise RuntimeError("rank %d register failed: %s" % (rank, err))
+        reg_rc = rc
         rc, rtt_us = prep.heartbeat(client)
         phase_time["reg"] += t1 - t0
         phase_time["hb"] += time.perf_counter() - t1
         if rc != 0:
             raise RuntimeError("rank %d heartbeat failed: %s" % (rank, ra.error_name(rc)))
+        last.update(register_rc=reg_rc, znodes=znodes, heartbeat_rc=rc)
         return rtt_us
 
     # ---- warmup ----
@@ -273,6 +328,9 @@ def main():
     elapsed = time.perf_counter() - t0
     stat_after = read_cpu_stat() if rank == 0 else None
     barrier()
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank, world)
 
     # max elapsed over ranks is THE job time; p50 over all ranks' heartbeats
     if dist is not None:
