@@ -1,7 +1,7 @@
 # Build the native core: the pybind11 extension (in-tree) and the standalone
 # binaries (registrard daemon + zkensembled synthetic-ensemble server).
 CXX ?= g++
-CXXFLAGS ?= -std=c++17 -O2 -g -Wall -pthread
+CXXFLAGS ?= -std=c++20 -O2 -g -Wall -pthread
 SRCDIR := registrar_amd/csrc
 BINDIR := bin
 
@@ -9,7 +9,7 @@ CORE_SRCS := $(SRCDIR)/ensemble.cpp $(SRCDIR)/zkclient.cpp $(SRCDIR)/registrar.c
              $(SRCDIR)/health.cpp $(SRCDIR)/orchestrator.cpp $(SRCDIR)/gpu.cpp
 HDRS := $(wildcard $(SRCDIR)/*.hpp)
 
-.PHONY: all ext daemon test check clean tsan asan stress
+.PHONY: all ext daemon test check clean tsan asan stress hotpath
 
 all: ext daemon
 
@@ -43,6 +43,13 @@ $(BINDIR)/stress: $(SRCDIR)/stress_main.cpp $(CORE_SRCS) $(HDRS)
 	@mkdir -p $(BINDIR)
 	$(CXX) $(CXXFLAGS) -o $@ $(SRCDIR)/stress_main.cpp $(CORE_SRCS)
 
+# per-thread CPU / allocation profile of the bench.py cycle (docs/perf_hotpath.md)
+hotpath: $(BINDIR)/hotpath
+
+$(BINDIR)/hotpath: $(SRCDIR)/hotpath_main.cpp $(CORE_SRCS) $(HDRS)
+	@mkdir -p $(BINDIR)
+	$(CXX) $(CXXFLAGS) -o $@ $(SRCDIR)/hotpath_main.cpp $(CORE_SRCS)
+
 # gcc-11's libtsan mismodels this glibc's condition_variable timed waits
 # (verified false positives on a textbook cv program), so sanitizer builds
 # use ROCm's LLVM toolchain instead.
@@ -50,13 +57,13 @@ SANCXX ?= /opt/rocm/lib/llvm/bin/clang++
 
 tsan: $(SRCDIR)/stress_main.cpp $(CORE_SRCS) $(HDRS)
 	@mkdir -p $(BINDIR)
-	$(SANCXX) -std=c++17 -O1 -g -fsanitize=thread -pthread -o $(BINDIR)/stress_tsan \
+	$(SANCXX) -std=c++20 -O1 -g -fsanitize=thread -pthread -o $(BINDIR)/stress_tsan \
 		$(SRCDIR)/stress_main.cpp $(CORE_SRCS)
 	TSAN_OPTIONS="halt_on_error=1" $(BINDIR)/stress_tsan -c 4 -t 8
 
 asan: $(SRCDIR)/stress_main.cpp $(CORE_SRCS) $(HDRS)
 	@mkdir -p $(BINDIR)
-	$(SANCXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -pthread \
+	$(SANCXX) -std=c++20 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -pthread \
 		-o $(BINDIR)/stress_asan $(SRCDIR)/stress_main.cpp $(CORE_SRCS)
 	$(BINDIR)/stress_asan -c 4 -t 8
 

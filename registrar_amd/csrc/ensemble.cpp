@@ -53,42 +53,52 @@ int64_t wall_ms() {
   return static_cast<int64_t>(ts.tv_sec) * 1000 + ts.tv_nsec / 1000000;
 }
 
-std::string parent_path(const std::string& p) {
+// Parent of a path as a view of the same bytes ("/" for depth-1 paths).
+std::string_view parent_view(std::string_view p) {
   size_t pos = p.rfind('/');
-  if (pos == std::string::npos || pos == 0) return "/";
+  if (pos == std::string_view::npos || pos == 0) return "/";
   return p.substr(0, pos);
 }
 
-std::string basename_of(const std::string& p) {
-  size_t pos = p.rfind('/');
-  return p.substr(pos + 1);
-}
-
-bool valid_path(const std::string& p) {
+bool valid_path(std::string_view p) {
   if (p.empty() || p[0] != '/') return false;
   if (p.size() > 1 && p.back() == '/') return false;
-  if (p.find("//") != std::string::npos) return false;
+  if (p.find("//") != std::string_view::npos) return false;
   return true;
 }
+
+// Tree and watch maps are keyed by (path, hash of path). A request hashes its
+// path once: the same value picks the shard and probes the map, and lookups
+// go by view (C++20 heterogeneous lookup) so no std::string is built to find
+// a node. The map key is the one owning copy of a path.
+struct PathKey {
+  std::string path;
+  size_t hash;
+};
+struct PathRef {
+  std::string_view path;
+  size_t hash;
+};
+inline PathRef ref_of(std::string_view p) { return {p, std::hash<std::string_view>{}(p)}; }
+inline PathRef ref_of(const PathKey& k) { return {k.path, k.hash}; }
+struct PathHash {
+  using is_transparent = void;
+  size_t operator()(const PathKey& k) const noexcept { return k.hash; }
+  size_t operator()(const PathRef& r) const noexcept { return r.hash; }
+};
+struct PathEq {
+  using is_transparent = void;
+  bool operator()(const PathKey& a, const PathKey& b) const noexcept { return a.path == b.path; }
+  bool operator()(const PathKey& a, const PathRef& b) const noexcept { return a.path == b.path; }
+  bool operator()(const PathRef& a, const PathKey& b) const noexcept { return a.path == b.path; }
+};
 
 }  // namespace
 
 struct Ensemble::Impl {
   static constexpr size_t kShards = 64;
 
-  struct ZNode {
-    std::string data;
-    Stat stat;
-    // unordered: create/delete are the hot path; listings sort on demand
-    std::unordered_set<std::string> children;
-  };
-
-  struct Shard {
-    std::mutex mu;
-    std::unordered_map<std::string, ZNode> nodes;
-    std::unordered_map<std::string, std::set<int64_t>> data_watches;
-    std::unordered_map<std::string, std::set<int64_t>> child_watches;
-  };
+  struct ZNode;
 
   struct Session {
     int64_t id = 0;
@@ -96,11 +106,54 @@ struct Ensemble::Impl {
     int timeout_ms = 30000;
     std::atomic<int64_t> last_touch{0};  // monotonic ms, lock-free touch
     std::atomic<uint64_t> conn_id{0};    // 0 = detached
-    std::atomic<bool> alive{true};       // false once kill_session starts
+    // false once kill_session starts; written under eph_mu, so a create that
+    // reads it under eph_mu either links before the kill's drain or not at all
+    std::atomic<bool> alive{true};
     std::mutex eph_mu;
-    std::unordered_set<std::string> ephemerals;
+    // this session's ephemerals: intrusive list through ZNode::eph_prev/next
+    // (no per-create allocation, no second copy of the path)
+    ZNode* eph_head = nullptr;
+    size_t eph_count = 0;
   };
   using SessionPtr = std::shared_ptr<Session>;
+
+  // Map nodes are address-stable, so the tree links nodes by pointer:
+  //   - key points at the node's own map key (its path; immutable),
+  //   - first_child / nchildren and the children's parent / sib_prev /
+  //     sib_next are guarded by THIS node's shard lock (a child is only ever
+  //     created or removed with its parent's shard locked, and a node with
+  //     children cannot be removed),
+  //   - owner / eph_prev / eph_next / eph_linked are guarded by the owner
+  //     session's eph_mu (taken inside the shard locks: shard → eph_mu).
+  struct ZNode {
+    std::string data;
+    Stat stat;
+    const PathKey* key = nullptr;
+    ZNode* parent = nullptr;
+    ZNode* first_child = nullptr;
+    ZNode* sib_prev = nullptr;
+    ZNode* sib_next = nullptr;
+    int32_t nchildren = 0;
+    SessionPtr owner;  // ephemeral owner (null for persistent nodes)
+    ZNode* eph_prev = nullptr;
+    ZNode* eph_next = nullptr;
+    bool eph_linked = false;
+
+    std::string_view name() const {
+      std::string_view p = key->path;
+      return p.substr(p.rfind('/') + 1);
+    }
+  };
+
+  using NodeMap = std::unordered_map<PathKey, ZNode, PathHash, PathEq>;
+  using WatchMap = std::unordered_map<PathKey, std::set<int64_t>, PathHash, PathEq>;
+
+  struct Shard {
+    std::mutex mu;
+    NodeMap nodes;
+    WatchMap data_watches;
+    WatchMap child_watches;
+  };
 
   struct Conn {
     uint64_t id = 0;
@@ -108,14 +161,31 @@ struct Ensemble::Impl {
     size_t server_idx = 0;  // which server (port) accepted it — kill semantics
     size_t io_idx = 0;      // which IO loop owns its events
     // owner-loop-thread only:
-    std::string inbuf;
-    size_t inpos = 0;
+    RecvBuf inbuf;
     bool handshaken = false;
     SessionPtr session;  // cached after handshake (lock-free touch)
     bool flush_scheduled = false;
-    // shared output state:
+    // per event drain (on_conn_event): both clocks are read once, and the
+    // last parent path seen is remembered as (view into inbuf, hash) so a run
+    // of siblings hashes its parent once. Only the path's hash is cached,
+    // nothing about the tree.
+    int64_t drain_mono_ms = 0;
+    int64_t drain_wall_ms = 0;
+    PathRef last_parent{std::string_view(), 0};
+    // replies produced during a drain are staged here without a lock and
+    // move to outbuf once, at the flush that ends the drain
+    std::string stage;
+    std::atomic<size_t> stage_pub{0};  // stage.size() after the last whole packet
+    // shared output state (out_mu):
     std::mutex out_mu;
     std::string outbuf;
+    // true while the owner loop is inside a drain (written under out_mu by
+    // the owner; the owner may read it without the lock)
+    bool draining = false;
+    // packets delivered by OTHER threads during a drain, each with the stage
+    // position it arrived at, so the flush can interleave them exactly where
+    // a locked append would have put them
+    std::vector<std::pair<size_t, std::string>> xq;
     bool epollout_armed = false;
     bool closing = false;  // close once outbuf drains
     std::atomic<bool> dead{false};
@@ -128,10 +198,16 @@ struct Ensemble::Impl {
     bool up = false;
   };
 
-  struct OpCounters {
+  // One counter block per IO loop (slot = io_idx % kCounterSlots), each on
+  // cache lines of its own, so IO threads do not bounce a shared line on
+  // every request; counters() sums the slots. Increments stay atomic RMWs so
+  // loops that share a slot (more than kCounterSlots IO threads) still count
+  // exactly.
+  struct alignas(128) OpCounters {
     std::atomic<uint64_t> connect{0}, create{0}, del{0}, exists{0}, get_data{0}, set_data{0},
         get_children{0}, ping{0}, close_session{0}, unknown{0};
   };
+  static constexpr size_t kCounterSlots = 16;
 
   EnsembleConfig cfg;
   Logger log;
@@ -141,7 +217,8 @@ struct Ensemble::Impl {
   std::atomic<bool> started{false};
   std::atomic<int> latency_ms{0};
   std::atomic<int64_t> zxid_counter{0};
-  OpCounters ops;
+  std::array<OpCounters, kCounterSlots> ops;
+  OpCounters& cnt(const Conn* c) { return ops[c->io_idx % kCounterSlots]; }
 
   std::array<Shard, kShards> shards;
 
@@ -163,24 +240,19 @@ struct Ensemble::Impl {
   explicit Impl(EnsembleConfig c) : cfg(std::move(c)), log(Logger("zk-ensemble").child("ensemble")) {
     log.set_level(cfg.log_level);
     latency_ms.store(cfg.latency_ms);
-    shard_of("/").nodes["/"] = ZNode{};
+    PathRef root = ref_of("/");
+    emplace_node(shards[root.hash % kShards], root);
   }
 
-  Shard& shard_of(const std::string& path) {
-    return shards[std::hash<std::string>{}(path) % kShards];
-  }
-  size_t shard_idx(const std::string& path) const {
-    return std::hash<std::string>{}(path) % kShards;
-  }
+  Shard& shard_of(const PathRef& r) { return shards[r.hash % kShards]; }
+  Shard& shard_of(std::string_view path) { return shard_of(ref_of(path)); }
 
-  // Lock the shards of two paths without deadlock (index order; may be same).
-  // Exposes the shard refs so callers hash each path exactly once.
+  // Lock two shards without deadlock (index order; may be the same shard).
   struct TwoShardLock {
     std::unique_lock<std::mutex> a, b;
-    Shard* first;   // shard of p1
-    Shard* second;  // shard of p2
-    TwoShardLock(Impl& impl, const std::string& p1, const std::string& p2) {
-      size_t i1 = impl.shard_idx(p1), i2 = impl.shard_idx(p2);
+    Shard* first;   // shard i1
+    Shard* second;  // shard i2
+    TwoShardLock(Impl& impl, size_t i1, size_t i2) {
       first = &impl.shards[i1];
       second = &impl.shards[i2];
       if (i1 == i2) {
@@ -190,7 +262,116 @@ struct Ensemble::Impl {
         b = std::unique_lock<std::mutex>(impl.shards[std::max(i1, i2)].mu);
       }
     }
+    TwoShardLock(Impl& impl, const PathRef& p1, const PathRef& p2)
+        : TwoShardLock(impl, p1.hash % kShards, p2.hash % kShards) {}
   };
+
+  // ---------------- tree primitives (shard locks held) ----------------
+
+  // the node at r in whichever shard r hashes to, or null
+  ZNode* find_node(const PathRef& r) {
+    Shard& sh = shard_of(r);
+    auto it = sh.nodes.find(r);
+    return it == sh.nodes.end() ? nullptr : &it->second;
+  }
+
+  // r must not exist in sh; the key string built here is the path's one
+  // owning copy
+  ZNode& emplace_node(Shard& sh, const PathRef& r) {
+    auto res = sh.nodes.emplace(std::piecewise_construct,
+                                std::forward_as_tuple(PathKey{std::string(r.path), r.hash}),
+                                std::forward_as_tuple());
+    res.first->second.key = &res.first->first;
+    return res.first->second;
+  }
+
+  static void link_child(ZNode& par, ZNode& ch) {
+    ch.parent = &par;
+    ch.sib_prev = nullptr;
+    ch.sib_next = par.first_child;
+    if (par.first_child) par.first_child->sib_prev = &ch;
+    par.first_child = &ch;
+    par.nchildren++;
+  }
+
+  static void unlink_child(ZNode& ch) {
+    ZNode* par = ch.parent;
+    if (!par) return;
+    if (ch.sib_prev)
+      ch.sib_prev->sib_next = ch.sib_next;
+    else
+      par->first_child = ch.sib_next;
+    if (ch.sib_next) ch.sib_next->sib_prev = ch.sib_prev;
+    par->nchildren--;
+    ch.parent = ch.sib_prev = ch.sib_next = nullptr;
+  }
+
+  // sorted child names (listings sort on demand; create/delete are O(1))
+  static void list_children(const ZNode& n, std::vector<std::string>* out) {
+    out->clear();
+    out->reserve(static_cast<size_t>(n.nchildren));
+    for (const ZNode* c = n.first_child; c; c = c->sib_next) out->emplace_back(c->name());
+    std::sort(out->begin(), out->end());
+  }
+
+  // s.eph_mu held
+  static void eph_link(Session& s, ZNode& n) {
+    n.eph_prev = nullptr;
+    n.eph_next = s.eph_head;
+    if (s.eph_head) s.eph_head->eph_prev = &n;
+    s.eph_head = &n;
+    n.eph_linked = true;
+    s.eph_count++;
+  }
+
+  // s.eph_mu held
+  static void eph_unlink(Session& s, ZNode& n) {
+    if (!n.eph_linked) return;
+    if (n.eph_prev)
+      n.eph_prev->eph_next = n.eph_next;
+    else
+      s.eph_head = n.eph_next;
+    if (n.eph_next) n.eph_next->eph_prev = n.eph_prev;
+    n.eph_prev = n.eph_next = nullptr;
+    n.eph_linked = false;
+    s.eph_count--;
+  }
+
+  // Take a node that is about to be erased out of its owner's ephemeral
+  // index. Runs inside the node's shard lock, BEFORE the erase: the index
+  // holds node pointers, so a node must never be freed while linked.
+  static void detach_ephemeral(ZNode& n) {
+    if (!n.owner) return;
+    std::lock_guard<std::mutex> eg(n.owner->eph_mu);
+    eph_unlink(*n.owner, n);
+  }
+
+  // Remove the node at `it` (no children; its shard csh and its parent's
+  // shard psh both locked): session index, parent link + parent Stat,
+  // watches (parent's child watch first, then NodeDeleted), erase. Returns
+  // the zxid the removal committed at.
+  int64_t remove_node_locked(Shard& csh, NodeMap::iterator it, Shard& psh) {
+    ZNode& n = it->second;
+    int64_t z = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
+    detach_ephemeral(n);
+    if (ZNode* par = n.parent) {
+      unlink_child(n);
+      par->stat.cversion++;
+      par->stat.pzxid = z;
+      par->stat.num_children = par->nchildren;
+      fire_child_watches_locked(psh, ref_of(*par->key));
+    }
+    fire_deleted_watches_locked(csh, ref_of(it->first));
+    csh.nodes.erase(it);
+    return z;
+  }
+
+  // The parent of a request path, hashed once per run of siblings within one
+  // drain (pv must point into the connection's receive buffer).
+  PathRef parent_ref(Conn* c, std::string_view pv) {
+    if (c->last_parent.path.data() == nullptr || c->last_parent.path != pv) c->last_parent = ref_of(pv);
+    return c->last_parent;
+  }
 
   // ---------------- lifecycle ----------------
 
@@ -335,12 +516,15 @@ struct Ensemble::Impl {
       return;
     }
     if (ev & EPOLLIN) {
+      // read straight into the receive buffer's tail; frames are parsed in
+      // place and the buffer only moves here, before the handlers run
       bool eof = false;
-      char buf[65536];
       while (true) {
-        ssize_t n = read(c->fd, buf, sizeof(buf));
+        size_t room = 0;
+        char* dst = c->inbuf.tail(65536, &room);
+        ssize_t n = read(c->fd, dst, room);
         if (n > 0) {
-          c->inbuf.append(buf, static_cast<size_t>(n));
+          c->inbuf.commit(static_cast<size_t>(n));
         } else if (n == 0) {
           eof = true;  // process buffered frames (e.g. closeSession) first
           break;
@@ -351,10 +535,18 @@ struct Ensemble::Impl {
           break;
         }
       }
+      // once per drain: both clocks, the parent-hash cache, the staging state
+      c->drain_mono_ms = now_ms();
+      c->drain_wall_ms = wall_ms();
+      c->last_parent = PathRef{std::string_view(), 0};
+      {
+        std::lock_guard<std::mutex> og(c->out_mu);
+        c->draining = true;
+      }
       if (!process_frames(c.get())) return;
-      // replies queued during this drain go out in one flush (syscall
+      // replies staged during this drain go out in one flush (syscall
       // batching: 1k pipelined creates ⇒ a handful of large writes)
-      flush_out(c.get());
+      flush_out(c.get(), /*end_drain=*/true);
       if (c->dead.load()) return;  // flush_out may close on error/closing
       if (eof) {
         close_conn(c.get());
@@ -368,9 +560,9 @@ struct Ensemble::Impl {
   // returns false if the conn was closed
   bool process_frames(Conn* c) {
     while (!c->dead.load()) {
-      size_t avail = c->inbuf.size() - c->inpos;
+      size_t avail = c->inbuf.size();
       if (avail < 4) break;
-      const unsigned char* p = reinterpret_cast<const unsigned char*>(c->inbuf.data() + c->inpos);
+      const unsigned char* p = reinterpret_cast<const unsigned char*>(c->inbuf.ptr());
       uint32_t len = (static_cast<uint32_t>(p[0]) << 24) | (static_cast<uint32_t>(p[1]) << 16) |
                      (static_cast<uint32_t>(p[2]) << 8) | static_cast<uint32_t>(p[3]);
       if (len > 4 * 1024 * 1024) {  // jute.maxbuffer-ish sanity cap
@@ -378,22 +570,20 @@ struct Ensemble::Impl {
         return false;
       }
       if (avail < 4 + len) break;
-      const char* body = c->inbuf.data() + c->inpos + 4;
-      c->inpos += 4 + len;
+      // consumed frames stay where they are until the next read's tail():
+      // handlers hold views into them for the rest of the drain
+      const char* body = c->inbuf.ptr() + 4;
+      c->inbuf.consume(4 + len);
       if (!handle_frame(c, body, len)) {
         close_conn(c);
         return false;
       }
     }
-    if (c->inpos > 0) {
-      c->inbuf.erase(0, c->inpos);
-      c->inpos = 0;
-    }
     return true;
   }
 
   void touch(Conn* c) {
-    if (c->session) c->session->last_touch.store(now_ms(), std::memory_order_relaxed);
+    if (c->session) c->session->last_touch.store(c->drain_mono_ms, std::memory_order_relaxed);
   }
 
   // returns false ⇒ caller closes the conn (protocol error)
@@ -409,7 +599,7 @@ struct Ensemble::Impl {
       touch(c);
       switch (hdr.type) {
         case kOpPing:
-          ops.ping.fetch_add(1, std::memory_order_relaxed);
+          cnt(c).ping.fetch_add(1, std::memory_order_relaxed);
           send_reply(c, kXidPing, zxid_counter.load(std::memory_order_relaxed), kZOk, nullptr);
           break;
         case kOpCreate:
@@ -459,7 +649,7 @@ struct Ensemble::Impl {
           send_reply(c, hdr.xid, zxid_counter.load(std::memory_order_relaxed), kZOk, nullptr);
           break;
         default:
-          ops.unknown.fetch_add(1, std::memory_order_relaxed);
+          cnt(c).unknown.fetch_add(1, std::memory_order_relaxed);
           send_reply(c, hdr.xid, zxid_counter.load(std::memory_order_relaxed), kZSystemError, nullptr);
           break;
       }
@@ -467,13 +657,16 @@ struct Ensemble::Impl {
     } catch (const std::exception& e) {
       log.warn("ensemble: malformed frame, closing conn", {{"err", Json(e.what())}});
       return false;
+    } catch (...) {
+      // never unwind out of a drain: its staged replies would go unflushed
+      return false;
     }
   }
 
   void handle_connect(Conn* c, JuteReader& r) {
     ConnectRequest req;
     req.deserialize(r);
-    ops.connect.fetch_add(1, std::memory_order_relaxed);
+    cnt(c).connect.fetch_add(1, std::memory_order_relaxed);
     ConnectResponse resp;
     resp.has_read_only = req.has_read_only;
     bool expired_handshake = false;
@@ -550,104 +743,115 @@ struct Ensemble::Impl {
   // --- ops ---
 
   void handle_create(Conn* c, int32_t xid, JuteReader& r, bool with_stat = false) {
-    ops.create.fetch_add(1, std::memory_order_relaxed);
-    CreateRequest req;
-    req.deserialize(r);
+    cnt(c).create.fetch_add(1, std::memory_order_relaxed);
+    // parse in place: path and payload are views of the frame, which stays
+    // put in c->inbuf for the whole drain. The ACL vector is validated and
+    // skipped (the open-ACL server discards it).
+    std::string_view path = r.read_string_view();
+    std::string_view data = r.read_buffer_view();
+    int32_t nacl = r.read_vec_count(12);
+    for (int32_t i = 0; i < nacl; i++) {
+      r.read_int();     // perms
+      r.skip_string();  // scheme
+      r.skip_string();  // id
+    }
+    int32_t flags = r.read_int();
     int32_t err = kZOk;
-    CreateResponse resp;
     int64_t sid = sid_of(c);
-    bool made_ephemeral = false;
-    std::string created_path;
-    std::string child_watch_parent;
-    int64_t op_zxid = 0;   // the zxid THIS create committed at
-    Stat created_stat;     // snapshot for create2 replies
-    if (!valid_path(req.path) || req.path == "/") {
+    int64_t op_zxid = 0;  // the zxid THIS create committed at
+    Stat created_stat;    // snapshot for create2 replies
+    std::string seq_path;  // SEQUENCE only: the path with its suffix
+    std::string_view final_path = path;
+    if (!valid_path(path) || path == "/") {
       err = kZMarshallingError;
     } else {
-      std::string parent = parent_path(req.path);
-      TwoShardLock lk(*this, req.path, parent);
+      // one hash per path: it picks the shard and probes the map
+      PathRef cref = ref_of(path);
+      PathRef pref = parent_ref(c, parent_view(path));
+      TwoShardLock lk(*this, cref, pref);
       Shard& psh = *lk.second;
-      auto pit = psh.nodes.find(parent);
+      auto pit = psh.nodes.find(pref);
       if (pit == psh.nodes.end()) {
         err = kZNoNode;
       } else if (pit->second.stat.ephemeral_owner != 0) {
         err = kZNoChildrenForEphemerals;
       } else {
-        std::string path = req.path;
-        if (req.flags & kSequence) {
-          char suffix[16];
-          snprintf(suffix, sizeof(suffix), "%010d", pit->second.stat.cversion);
-          path += suffix;
-        }
-        // NB: with SEQUENCE the final path may hash to a different shard than
-        // req.path; re-lock correctly in that (registrar-unused) corner
-        Shard& csh = (req.flags & kSequence) ? shard_of(path) : *lk.first;
-        bool same_lock = (&csh == lk.first) || (&csh == &psh);
+        ZNode& par = pit->second;
+        Shard* csh = lk.first;
         std::unique_lock<std::mutex> extra;
-        if (!same_lock) extra = std::unique_lock<std::mutex>(csh.mu, std::try_to_lock);
-        if (!same_lock && !extra.owns_lock()) {
-          err = kZSystemError;  // pathological shard collision; not reachable
-                                // for non-sequence creates
-        } else if (auto [nit, inserted] = csh.nodes.try_emplace(path); !inserted) {
-          err = kZNodeExists;
-        } else {
-          // single hash+probe: the node was emplaced above; fill it in
+        if (flags & kSequence) {
+          char suffix[16];
+          snprintf(suffix, sizeof(suffix), "%010d", par.stat.cversion);
+          seq_path.reserve(path.size() + 10);
+          seq_path.assign(path);
+          seq_path += suffix;
+          final_path = seq_path;
+          cref = ref_of(final_path);
+          // NB: with SEQUENCE the final path may hash to a different shard
+          // than the request path; lock it too in that (registrar-unused)
+          // corner
+          csh = &shard_of(cref);
+          if (csh != lk.first && csh != &psh) {
+            extra = std::unique_lock<std::mutex>(csh->mu, std::try_to_lock);
+            if (!extra.owns_lock()) err = kZSystemError;  // pathological shard collision
+          }
+        }
+        // Ephemeral creates and session death. kill_session clears `alive`
+        // under eph_mu and only then drains the session's index, one node at
+        // a time, each pop under eph_mu again. We check `alive` and link the
+        // new node inside ONE eph_mu critical section (held across the
+        // insert), so exactly one of two things happens:
+        //   - we saw alive: the node is in the index before the kill can
+        //     take eph_mu to clear the flag, so the drain finds and removes
+        //     it;
+        //   - we saw !alive: nothing is inserted and the create fails with
+        //     SESSION_EXPIRED.
+        // No ephemeral can therefore outlive its session, and unlike a
+        // create-then-roll-back no half-registered node is ever visible.
+        // Lock order: shard(s) → eph_mu (kill_session holds eph_mu alone).
+        Session* owner = nullptr;
+        std::unique_lock<std::mutex> eg;
+        if (err == kZOk && (flags & kEphemeral)) {
+          owner = c->session.get();
+          if (owner) {
+            eg = std::unique_lock<std::mutex>(owner->eph_mu);
+            if (!owner->alive.load(std::memory_order_relaxed)) owner = nullptr;
+          }
+          if (!owner) err = kZSessionExpired;
+        }
+        if (err == kZOk && csh->nodes.find(cref) != csh->nodes.end()) err = kZNodeExists;
+        if (err == kZOk) {
           int64_t zz = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
           op_zxid = zz;
-          ZNode& n = nit->second;
-          n.data = req.data;
+          ZNode& n = emplace_node(*csh, cref);
+          n.data.assign(data.data(), data.size());
           n.stat.czxid = zz;
           n.stat.mzxid = zz;
-          n.stat.ctime = wall_ms();
+          n.stat.ctime = c->drain_wall_ms;
           n.stat.mtime = n.stat.ctime;
-          n.stat.data_length = static_cast<int32_t>(req.data.size());
-          if (req.flags & kEphemeral) {
+          n.stat.data_length = static_cast<int32_t>(data.size());
+          if (owner) {
             n.stat.ephemeral_owner = sid;
-            made_ephemeral = true;
+            n.owner = c->session;
+            eph_link(*owner, n);
+            eg.unlock();
           }
-          ZNode& par = pit->second;
-          par.children.insert(basename_of(path));
+          link_child(par, n);
           par.stat.cversion++;
           par.stat.pzxid = zz;
-          par.stat.num_children = static_cast<int32_t>(par.children.size());
-          fire_data_watches_locked(csh, path, kEventNodeCreated);
-          fire_child_watches_locked(psh, parent);
-          resp.path = path;
-          created_path = path;
+          par.stat.num_children = par.nchildren;
+          fire_data_watches_locked(*csh, cref, kEventNodeCreated);
+          fire_child_watches_locked(psh, pref);
           created_stat = n.stat;
         }
       }
-      (void)child_watch_parent;
-    }
-    if (made_ephemeral) {
-      // Registered outside the shard locks — NO global lock on this hot path.
-      // kill_session flips `alive` BEFORE draining the set, so: insert seen
-      // by the drain ⇒ cleaned there; insert after the drain ⇒ alive==false
-      // here ⇒ roll the node back ourselves.
-      SessionPtr s = c->session;
-      bool ok = false;
-      if (s) {
-        {
-          std::lock_guard<std::mutex> eg(s->eph_mu);
-          s->ephemerals.insert(created_path);
-        }
-        ok = s->alive.load(std::memory_order_acquire);
-        if (!ok) {
-          std::lock_guard<std::mutex> eg(s->eph_mu);
-          ok = s->ephemerals.count(created_path) == 0;  // drain took it: fine
-          if (!ok) s->ephemerals.erase(created_path);
-        }
-      }
-      if (!ok) {
-        delete_node(created_path, s);
-        err = kZSessionExpired;
-      }
     }
     // mutating replies carry the op's OWN zxid (a fresh counter read could
-    // exceed what this client actually observed — ADVICE r1)
+    // exceed what this client actually observed — ADVICE r1). The path goes
+    // out straight from the request bytes (or the SEQUENCE path).
     if (err == kZOk)
       send_reply(c, xid, op_zxid, kZOk, [&](JuteWriter& w) {
-        resp.serialize(w);
+        w.write_string(final_path);                // CreateResponse
         if (with_stat) created_stat.serialize(w);  // Create2Response
       });
     else
@@ -655,116 +859,91 @@ struct Ensemble::Impl {
   }
 
   void handle_delete(Conn* c, int32_t xid, JuteReader& r) {
-    ops.del.fetch_add(1, std::memory_order_relaxed);
-    DeleteRequest req;
-    req.deserialize(r);
+    cnt(c).del.fetch_add(1, std::memory_order_relaxed);
+    std::string_view path = r.read_string_view();
+    int32_t version = r.read_int();
     int32_t err = kZOk;
     int64_t op_zxid = 0;
     {
-      // peek under the target's shard lock; full delete re-locks both shards
-      Shard& sh = shard_of(req.path);
-      std::unique_lock<std::mutex> lk(sh.mu);
-      auto it = sh.nodes.find(req.path);
-      if (it == sh.nodes.end() || req.path == "/") {
+      // one critical section: both shards locked once, checks and removal
+      // together
+      PathRef cref = ref_of(path);
+      PathRef pref = parent_ref(c, parent_view(path));
+      TwoShardLock lk(*this, cref, pref);
+      Shard& csh = *lk.first;
+      auto it = csh.nodes.find(cref);
+      if (it == csh.nodes.end() || path == "/") {
         err = kZNoNode;
-      } else if (!it->second.children.empty()) {
+      } else if (it->second.nchildren != 0) {
         err = kZNotEmpty;
-      } else if (req.version != -1 && req.version != it->second.stat.version) {
+      } else if (version != -1 && version != it->second.stat.version) {
         err = kZBadVersion;
+      } else {
+        op_zxid = remove_node_locked(csh, it, *lk.second);
       }
-    }
-    if (err == kZOk) {
-      // common case: a session unlinking its own ephemerals (cleanup step)
-      if (!delete_node(req.path, c->session, &op_zxid)) err = kZNoNode;  // raced
     }
     send_reply(c, xid,
                op_zxid ? op_zxid : zxid_counter.load(std::memory_order_relaxed),
                err, nullptr);
   }
 
-  // Full node removal: locks child+parent shards, updates parent, fires
-  // watches, detaches from the owner session. Returns false if missing.
-  // owner_hint avoids the session_mu map lookup on the hot path (a session
-  // deleting its own ephemerals — the register-pipeline cleanup case).
-  bool delete_node(const std::string& path, const SessionPtr& owner_hint = nullptr,
-                   int64_t* out_zxid = nullptr) {
-    int64_t owner = 0;
-    {
-      std::string parent = parent_path(path);
-      TwoShardLock lk(*this, path, parent);
-      Shard& csh = *lk.first;
-      auto it = csh.nodes.find(path);
-      if (it == csh.nodes.end()) return false;
-      if (!it->second.children.empty()) return false;  // re-check under lock
-      int64_t z = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
-      if (out_zxid) *out_zxid = z;
-      owner = it->second.stat.ephemeral_owner;
-      csh.nodes.erase(it);
-      Shard& psh = *lk.second;
-      auto pit = psh.nodes.find(parent);
-      if (pit != psh.nodes.end()) {
-        pit->second.children.erase(basename_of(path));
-        pit->second.stat.cversion++;
-        pit->second.stat.pzxid = z;
-        pit->second.stat.num_children = static_cast<int32_t>(pit->second.children.size());
-        fire_child_watches_locked(psh, parent);
-      }
-      fire_deleted_watches_locked(csh, path);
-    }
-    if (owner != 0) {
-      SessionPtr s;
-      if (owner_hint && owner_hint->id == owner) {
-        s = owner_hint;
-      } else {
-        std::lock_guard<std::mutex> g(session_mu);
-        auto sit = sessions.find(owner);
-        if (sit != sessions.end()) s = sit->second;
-      }
-      if (s) {
-        std::lock_guard<std::mutex> eg(s->eph_mu);
-        s->ephemerals.erase(path);
-      }
-    }
+  // Full node removal for the callers that have only a path (session kill,
+  // rollback): locks child+parent shards, updates parent, fires watches,
+  // detaches from the owner session. Returns false if missing or not empty.
+  // only_owner: remove the node only if it is that session's ephemeral.
+  bool delete_node(std::string_view path, int64_t* out_zxid = nullptr, const Session* only_owner = nullptr) {
+    PathRef cref = ref_of(path);
+    PathRef pref = ref_of(parent_view(path));
+    TwoShardLock lk(*this, cref, pref);
+    Shard& csh = *lk.first;
+    auto it = csh.nodes.find(cref);
+    if (it == csh.nodes.end()) return false;
+    if (it->second.nchildren != 0 || it->second.parent == nullptr) return false;
+    if (only_owner && it->second.owner.get() != only_owner) return false;
+    int64_t z = remove_node_locked(csh, it, *lk.second);
+    if (out_zxid) *out_zxid = z;
     return true;
   }
 
   void handle_exists(Conn* c, int32_t xid, JuteReader& r) {
-    ops.exists.fetch_add(1, std::memory_order_relaxed);
-    ExistsRequest req;
-    req.deserialize(r);
+    cnt(c).exists.fetch_add(1, std::memory_order_relaxed);
+    std::string_view path = r.read_string_view();
+    bool watch = r.read_bool();
     int32_t err = kZOk;
-    ExistsResponse resp;
+    Stat stat;
     {
-      Shard& sh = shard_of(req.path);
+      PathRef ref = ref_of(path);
+      Shard& sh = shard_of(ref);
       std::lock_guard<std::mutex> lk(sh.mu);
-      if (req.watch) sh.data_watches[req.path].insert(sid_of(c));
-      auto it = sh.nodes.find(req.path);
+      if (watch) watch_set(sh.data_watches, ref).insert(sid_of(c));
+      auto it = sh.nodes.find(ref);
       if (it == sh.nodes.end())
         err = kZNoNode;
       else
-        resp.stat = it->second.stat;
+        stat = it->second.stat;
     }
     if (err == kZOk)
       send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), kZOk,
-                 [&](JuteWriter& w) { resp.serialize(w); });
+                 [&](JuteWriter& w) { stat.serialize(w); });
     else
       send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), err, nullptr);
   }
 
   void handle_get_data(Conn* c, int32_t xid, JuteReader& r) {
-    ops.get_data.fetch_add(1, std::memory_order_relaxed);
-    GetDataRequest req;
-    req.deserialize(r);
+    cnt(c).get_data.fetch_add(1, std::memory_order_relaxed);
+    std::string_view path = r.read_string_view();
+    bool watch = r.read_bool();
     int32_t err = kZOk;
     GetDataResponse resp;
     {
-      Shard& sh = shard_of(req.path);
+      PathRef ref = ref_of(path);
+      Shard& sh = shard_of(ref);
       std::lock_guard<std::mutex> lk(sh.mu);
-      auto it = sh.nodes.find(req.path);
+      auto it = sh.nodes.find(ref);
       if (it == sh.nodes.end()) {
         err = kZNoNode;
       } else {
-        if (req.watch) sh.data_watches[req.path].insert(sid_of(c));
+        if (watch) watch_set(sh.data_watches, ref).insert(sid_of(c));
         resp.data = it->second.data;
         resp.stat = it->second.stat;
       }
@@ -777,55 +956,57 @@ struct Ensemble::Impl {
   }
 
   void handle_set_data(Conn* c, int32_t xid, JuteReader& r) {
-    ops.set_data.fetch_add(1, std::memory_order_relaxed);
-    SetDataRequest req;
-    req.deserialize(r);
+    cnt(c).set_data.fetch_add(1, std::memory_order_relaxed);
+    std::string_view path = r.read_string_view();
+    std::string_view data = r.read_buffer_view();
+    int32_t version = r.read_int();
     int32_t err = kZOk;
-    SetDataResponse resp;
+    Stat stat;
     int64_t op_zxid = 0;
     {
-      Shard& sh = shard_of(req.path);
+      PathRef ref = ref_of(path);
+      Shard& sh = shard_of(ref);
       std::lock_guard<std::mutex> lk(sh.mu);
-      auto it = sh.nodes.find(req.path);
+      auto it = sh.nodes.find(ref);
       if (it == sh.nodes.end()) {
         err = kZNoNode;
-      } else if (req.version != -1 && req.version != it->second.stat.version) {
+      } else if (version != -1 && version != it->second.stat.version) {
         err = kZBadVersion;
       } else {
         int64_t zz = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
         op_zxid = zz;
-        it->second.data = req.data;
+        it->second.data.assign(data.data(), data.size());
         it->second.stat.mzxid = zz;
-        it->second.stat.mtime = wall_ms();
+        it->second.stat.mtime = c->drain_wall_ms;
         it->second.stat.version++;
-        it->second.stat.data_length = static_cast<int32_t>(req.data.size());
-        fire_data_watches_locked(sh, req.path, kEventNodeDataChanged);
-        resp.stat = it->second.stat;
+        it->second.stat.data_length = static_cast<int32_t>(data.size());
+        fire_data_watches_locked(sh, ref, kEventNodeDataChanged);
+        stat = it->second.stat;
       }
     }
     if (err == kZOk)
       send_reply(c, xid, op_zxid, kZOk,
-                 [&](JuteWriter& w) { resp.serialize(w); });
+                 [&](JuteWriter& w) { stat.serialize(w); });
     else
       send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), err, nullptr);
   }
 
   void handle_get_children(Conn* c, int32_t xid, JuteReader& r) {
-    ops.get_children.fetch_add(1, std::memory_order_relaxed);
-    GetChildrenRequest req;
-    req.deserialize(r);
+    cnt(c).get_children.fetch_add(1, std::memory_order_relaxed);
+    std::string_view path = r.read_string_view();
+    bool watch = r.read_bool();
     int32_t err = kZOk;
     GetChildrenResponse resp;
     {
-      Shard& sh = shard_of(req.path);
+      PathRef ref = ref_of(path);
+      Shard& sh = shard_of(ref);
       std::lock_guard<std::mutex> lk(sh.mu);
-      auto it = sh.nodes.find(req.path);
+      auto it = sh.nodes.find(ref);
       if (it == sh.nodes.end()) {
         err = kZNoNode;
       } else {
-        if (req.watch) sh.child_watches[req.path].insert(sid_of(c));
-        resp.children.assign(it->second.children.begin(), it->second.children.end());
-        std::sort(resp.children.begin(), resp.children.end());
+        if (watch) watch_set(sh.child_watches, ref).insert(sid_of(c));
+        list_children(it->second, &resp.children);
       }
     }
     if (err == kZOk)
@@ -837,22 +1018,22 @@ struct Ensemble::Impl {
 
   // getChildren2: children + the node's Stat (3.4+ clients use it by default)
   void handle_get_children2(Conn* c, int32_t xid, JuteReader& r) {
-    ops.get_children.fetch_add(1, std::memory_order_relaxed);
-    GetChildrenRequest req;
-    req.deserialize(r);
+    cnt(c).get_children.fetch_add(1, std::memory_order_relaxed);
+    std::string_view path = r.read_string_view();
+    bool watch = r.read_bool();
     int32_t err = kZOk;
     GetChildrenResponse resp;
     Stat stat;
     {
-      Shard& sh = shard_of(req.path);
+      PathRef ref = ref_of(path);
+      Shard& sh = shard_of(ref);
       std::lock_guard<std::mutex> lk(sh.mu);
-      auto it = sh.nodes.find(req.path);
+      auto it = sh.nodes.find(ref);
       if (it == sh.nodes.end()) {
         err = kZNoNode;
       } else {
-        if (req.watch) sh.child_watches[req.path].insert(sid_of(c));
-        resp.children.assign(it->second.children.begin(), it->second.children.end());
-        std::sort(resp.children.begin(), resp.children.end());
+        if (watch) watch_set(sh.child_watches, ref).insert(sid_of(c));
+        list_children(it->second, &resp.children);
         stat = it->second.stat;
       }
     }
@@ -933,17 +1114,18 @@ struct Ensemble::Impl {
     std::vector<std::pair<std::string, int32_t>> data_events;   // path, event type
     std::vector<std::string> child_events;                      // parent paths
     std::vector<std::string> deleted_paths;                     // NodeDeleted → own child watchers
-    // ephemeral bookkeeping: (path, added, owner-session) — a delete may
-    // remove ANOTHER session's ephemeral; its owner's set must be updated
-    std::vector<std::tuple<std::string, bool, int64_t>> eph_changes;
+    // ephemerals this txn created but could not index because the session
+    // died mid-txn: rolled back after the shard locks are released
+    std::vector<std::string> rollback;
+    SessionPtr mine = c->session;
     int32_t txn_err = kZOk;
 
     {
       // lock every involved shard (paths + parents) in index order
       std::set<size_t> idxs;
       for (const auto& mo : mops) {
-        idxs.insert(shard_idx(mo.path));
-        idxs.insert(shard_idx(parent_path(mo.path)));
+        idxs.insert(ref_of(mo.path).hash % kShards);
+        idxs.insert(ref_of(parent_view(mo.path)).hash % kShards);
       }
       std::vector<std::unique_lock<std::mutex>> locks;
       locks.reserve(idxs.size());
@@ -956,11 +1138,7 @@ struct Ensemble::Impl {
         std::unordered_map<std::string, int> child_delta;
         std::unordered_map<std::string, int32_t> version;  // post-op versions
       } ov;
-      auto tree_node = [&](const std::string& p) -> ZNode* {
-        auto& sh = shard_of(p);
-        auto it = sh.nodes.find(p);
-        return it == sh.nodes.end() ? nullptr : &it->second;
-      };
+      auto tree_node = [&](const std::string& p) -> ZNode* { return find_node(ref_of(p)); };
       auto ov_exists = [&](const std::string& p) -> bool {
         auto it = ov.state.find(p);
         if (it != ov.state.end()) return it->second.first;
@@ -974,7 +1152,7 @@ struct Ensemble::Impl {
       };
       auto ov_child_count = [&](const std::string& p) -> int {
         ZNode* n = tree_node(p);
-        int base = n ? static_cast<int>(n->children.size()) : 0;
+        int base = n ? static_cast<int>(n->nchildren) : 0;
         auto it = ov.child_delta.find(p);
         return base + (it == ov.child_delta.end() ? 0 : it->second);
       };
@@ -993,7 +1171,7 @@ struct Ensemble::Impl {
         if (!valid_path(mo.path) || mo.path == "/") {
           err = (mo.type == kOpCreate && mo.path == "/") ? kZNodeExists : kZMarshallingError;
         } else {
-          std::string parent = parent_path(mo.path);
+          std::string parent(parent_view(mo.path));
           switch (mo.type) {
             case kOpCreate:
               if (mo.flags & kSequence) {
@@ -1060,32 +1238,38 @@ struct Ensemble::Impl {
         // ---- apply (all locks still held) ----
         for (size_t i = 0; i < mops.size(); i++) {
           const auto& mo = mops[i];
-          std::string parent = parent_path(mo.path);
+          std::string parent(parent_view(mo.path));
           switch (mo.type) {
             case kOpCreate: {
-              ops.create.fetch_add(1, std::memory_order_relaxed);
+              cnt(c).create.fetch_add(1, std::memory_order_relaxed);
               int64_t zz = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
               txn_zxid = zz;
-              Shard& csh = shard_of(mo.path);
-              ZNode& n = csh.nodes[mo.path];
+              PathRef cref = ref_of(mo.path);
+              ZNode& n = emplace_node(shard_of(cref), cref);  // validated absent above
               n.data = mo.data;
-              n.stat = Stat{};
               n.stat.czxid = zz;
               n.stat.mzxid = zz;
-              n.stat.ctime = wall_ms();
+              n.stat.ctime = c->drain_wall_ms;
               n.stat.mtime = n.stat.ctime;
               n.stat.data_length = static_cast<int32_t>(mo.data.size());
               if (mo.flags & kEphemeral) {
                 n.stat.ephemeral_owner = sid;
-                eph_changes.push_back({mo.path, true, sid});
+                if (mine) {
+                  // same alive/link handshake as handle_create; a create
+                  // that loses it is rolled back once the locks are released
+                  std::lock_guard<std::mutex> eg(mine->eph_mu);
+                  n.owner = mine;
+                  if (mine->alive.load(std::memory_order_relaxed))
+                    eph_link(*mine, n);
+                  else
+                    rollback.push_back(mo.path);
+                }
               }
-              Shard& psh = shard_of(parent);
-              auto pit = psh.nodes.find(parent);
-              if (pit != psh.nodes.end()) {
-                pit->second.children.insert(basename_of(mo.path));
-                pit->second.stat.cversion++;
-                pit->second.stat.pzxid = zz;
-                pit->second.stat.num_children = static_cast<int32_t>(pit->second.children.size());
+              if (ZNode* par = find_node(ref_of(parent))) {
+                link_child(*par, n);
+                par->stat.cversion++;
+                par->stat.pzxid = zz;
+                par->stat.num_children = par->nchildren;
               }
               data_events.push_back({mo.path, kEventNodeCreated});
               child_events.push_back(parent);
@@ -1093,23 +1277,22 @@ struct Ensemble::Impl {
               break;
             }
             case kOpDelete: {
-              ops.del.fetch_add(1, std::memory_order_relaxed);
+              cnt(c).del.fetch_add(1, std::memory_order_relaxed);
               int64_t zz = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
               txn_zxid = zz;
-              Shard& csh = shard_of(mo.path);
-              auto it = csh.nodes.find(mo.path);
+              PathRef cref = ref_of(mo.path);
+              Shard& csh = shard_of(cref);
+              auto it = csh.nodes.find(cref);
               if (it != csh.nodes.end()) {
-                if (it->second.stat.ephemeral_owner != 0)
-                  eph_changes.push_back({mo.path, false, it->second.stat.ephemeral_owner});
+                // may be ANOTHER session's ephemeral: leaves its owner's index
+                detach_ephemeral(it->second);
+                if (ZNode* par = it->second.parent) {
+                  unlink_child(it->second);
+                  par->stat.cversion++;
+                  par->stat.pzxid = zz;
+                  par->stat.num_children = par->nchildren;
+                }
                 csh.nodes.erase(it);
-              }
-              Shard& psh = shard_of(parent);
-              auto pit = psh.nodes.find(parent);
-              if (pit != psh.nodes.end()) {
-                pit->second.children.erase(basename_of(mo.path));
-                pit->second.stat.cversion++;
-                pit->second.stat.pzxid = zz;
-                pit->second.stat.num_children = static_cast<int32_t>(pit->second.children.size());
               }
               data_events.push_back({mo.path, kEventNodeDeleted});
               child_events.push_back(parent);
@@ -1117,18 +1300,16 @@ struct Ensemble::Impl {
               break;
             }
             case kOpSetData: {
-              ops.set_data.fetch_add(1, std::memory_order_relaxed);
+              cnt(c).set_data.fetch_add(1, std::memory_order_relaxed);
               int64_t zz = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
               txn_zxid = zz;
-              Shard& csh = shard_of(mo.path);
-              auto it = csh.nodes.find(mo.path);
-              if (it != csh.nodes.end()) {
-                it->second.data = mo.data;
-                it->second.stat.mzxid = zz;
-                it->second.stat.mtime = wall_ms();
-                it->second.stat.version++;
-                it->second.stat.data_length = static_cast<int32_t>(mo.data.size());
-                setdata_stats[i] = it->second.stat;
+              if (ZNode* n = find_node(ref_of(mo.path))) {
+                n->data = mo.data;
+                n->stat.mzxid = zz;
+                n->stat.mtime = c->drain_wall_ms;
+                n->stat.version++;
+                n->stat.data_length = static_cast<int32_t>(mo.data.size());
+                setdata_stats[i] = n->stat;
               }
               data_events.push_back({mo.path, kEventNodeDataChanged});
               break;
@@ -1139,49 +1320,26 @@ struct Ensemble::Impl {
         }
         // fire watches while holding the shard locks (same discipline as
         // the single-op handlers: shard → session_mu → conns_mu → out_mu)
-        for (auto& [path, ev] : data_events)
-          if (ev != kEventNodeDeleted) fire_data_watches_locked(shard_of(path), path, ev);
-        for (auto& path : deleted_paths) fire_deleted_watches_locked(shard_of(path), path);
+        for (auto& [path, ev] : data_events) {
+          PathRef ref = ref_of(path);
+          if (ev != kEventNodeDeleted) fire_data_watches_locked(shard_of(ref), ref, ev);
+        }
+        for (auto& path : deleted_paths) {
+          PathRef ref = ref_of(path);
+          fire_deleted_watches_locked(shard_of(ref), ref);
+        }
         std::set<std::string> fired;
-        for (auto& parent : child_events)
-          if (fired.insert(parent).second) fire_child_watches_locked(shard_of(parent), parent);
+        for (auto& parent : child_events) {
+          PathRef ref = ref_of(parent);
+          if (fired.insert(parent).second) fire_child_watches_locked(shard_of(ref), ref);
+        }
       }
     }
 
-    // session ephemeral bookkeeping outside the shard locks (same alive-flag
-    // handshake as single-op create); deletes may belong to OTHER sessions
-    if (txn_err == kZOk && !eph_changes.empty()) {
-      SessionPtr mine = c->session;
-      auto owner_session = [&](int64_t owner) -> SessionPtr {
-        if (mine && mine->id == owner) return mine;
-        std::lock_guard<std::mutex> g(session_mu);
-        auto sit = sessions.find(owner);
-        return sit == sessions.end() ? nullptr : sit->second;
-      };
-      for (auto& [path, added, owner] : eph_changes) {
-        SessionPtr s = owner_session(owner);
-        if (!s) continue;  // owner already dead; its drain saw (or will
-                           // no-op on) the node
-        std::lock_guard<std::mutex> eg(s->eph_mu);
-        if (added)
-          s->ephemerals.insert(path);
-        else
-          s->ephemerals.erase(path);
-      }
-      if (mine && !mine->alive.load(std::memory_order_acquire)) {
-        // our session died mid-txn: roll our created ephemerals back.
-        // Collect under eph_mu, delete after releasing it — delete_node's
-        // owner bookkeeping re-locks the same eph_mu (self-deadlock
-        // otherwise; caught by the chaos stress watchdog).
-        std::vector<std::string> rollback;
-        {
-          std::lock_guard<std::mutex> eg(mine->eph_mu);
-          for (auto& [path, added, owner] : eph_changes)
-            if (added && owner == mine->id && mine->ephemerals.erase(path)) rollback.push_back(path);
-        }
-        for (const auto& path : rollback) delete_node(path, mine);
-      }
-    }
+    // our session died mid-txn: remove the ephemerals it created but could
+    // not index (the session's drain never saw them). After the shard locks
+    // are released — delete_node takes them itself.
+    for (const auto& path : rollback) delete_node(path, nullptr, mine.get());
 
     // reply with THIS txn's last zxid (not a fresh counter read, which may
     // already reflect other connections' later commits)
@@ -1220,15 +1378,16 @@ struct Ensemble::Impl {
     for (const auto& path : req.data_watches) {
       bool fire_changed = false, fire_deleted = false;
       {
-        Shard& sh = shard_of(path);
+        PathRef ref = ref_of(path);
+        Shard& sh = shard_of(ref);
         std::lock_guard<std::mutex> lk(sh.mu);
-        auto it = sh.nodes.find(path);
+        auto it = sh.nodes.find(ref);
         if (it == sh.nodes.end())
           fire_deleted = true;
         else if (it->second.stat.mzxid > req.relative_zxid)
           fire_changed = true;
         else
-          sh.data_watches[path].insert(sid);
+          watch_set(sh.data_watches, ref).insert(sid);
       }
       if (fire_deleted) deliver_watch({sid}, path, kEventNodeDeleted);
       if (fire_changed) deliver_watch({sid}, path, kEventNodeDataChanged);
@@ -1236,28 +1395,30 @@ struct Ensemble::Impl {
     for (const auto& path : req.exist_watches) {
       bool fire_created = false;
       {
-        Shard& sh = shard_of(path);
+        PathRef ref = ref_of(path);
+        Shard& sh = shard_of(ref);
         std::lock_guard<std::mutex> lk(sh.mu);
-        auto it = sh.nodes.find(path);
+        auto it = sh.nodes.find(ref);
         if (it != sh.nodes.end())
           fire_created = true;  // appeared while the client was away
         else
-          sh.data_watches[path].insert(sid);
+          watch_set(sh.data_watches, ref).insert(sid);
       }
       if (fire_created) deliver_watch({sid}, path, kEventNodeCreated);
     }
     for (const auto& path : req.child_watches) {
       bool fire_child = false, fire_deleted = false;
       {
-        Shard& sh = shard_of(path);
+        PathRef ref = ref_of(path);
+        Shard& sh = shard_of(ref);
         std::lock_guard<std::mutex> lk(sh.mu);
-        auto it = sh.nodes.find(path);
+        auto it = sh.nodes.find(ref);
         if (it == sh.nodes.end())
           fire_deleted = true;
         else if (it->second.stat.pzxid > req.relative_zxid)
           fire_child = true;
         else
-          sh.child_watches[path].insert(sid);
+          watch_set(sh.child_watches, ref).insert(sid);
       }
       if (fire_deleted) deliver_watch({sid}, path, kEventNodeDeleted);
       if (fire_child) deliver_watch({sid}, path, kEventNodeChildrenChanged);
@@ -1279,9 +1440,10 @@ struct Ensemble::Impl {
     int32_t err = kZOk;
     Stat stat;
     {
-      Shard& sh = shard_of(path);
+      PathRef ref = ref_of(path);
+      Shard& sh = shard_of(ref);
       std::lock_guard<std::mutex> lk(sh.mu);
-      auto it = sh.nodes.find(path);
+      auto it = sh.nodes.find(ref);
       if (it == sh.nodes.end())
         err = kZNoNode;
       else
@@ -1303,9 +1465,10 @@ struct Ensemble::Impl {
     int32_t err = kZOk;
     Stat stat;
     {
-      Shard& sh = shard_of(path);
+      PathRef ref = ref_of(path);
+      Shard& sh = shard_of(ref);
       std::lock_guard<std::mutex> lk(sh.mu);
-      auto it = sh.nodes.find(path);
+      auto it = sh.nodes.find(ref);
       if (it == sh.nodes.end()) {
         err = kZNoNode;
       } else {
@@ -1321,7 +1484,7 @@ struct Ensemble::Impl {
   }
 
   void handle_close_session(Conn* c, int32_t xid) {
-    ops.close_session.fetch_add(1, std::memory_order_relaxed);
+    cnt(c).close_session.fetch_add(1, std::memory_order_relaxed);
     int64_t sid = sid_of(c);
     {
       std::lock_guard<std::mutex> og(c->out_mu);
@@ -1345,13 +1508,28 @@ struct Ensemble::Impl {
       s = it->second;
       sessions.erase(it);
     }
-    s->alive.store(false, std::memory_order_release);
-    std::unordered_set<std::string> eph;
     {
+      // under eph_mu: a create links a node only if it reads alive==true
+      // inside its own eph_mu section, so everything ever linked is linked
+      // before this store and is found by the drain below (handle_create
+      // has the full argument)
       std::lock_guard<std::mutex> eg(s->eph_mu);
-      eph.swap(s->ephemerals);
+      s->alive.store(false, std::memory_order_release);
     }
-    for (const auto& p : eph) delete_node(p, s);
+    // Drain one node at a time: pop it under eph_mu (a linked node cannot be
+    // freed — whoever removes it must take eph_mu to unlink it first), copy
+    // its path, then delete by path with no lock held, as before.
+    std::string p;
+    while (true) {
+      {
+        std::lock_guard<std::mutex> eg(s->eph_mu);
+        ZNode* n = s->eph_head;
+        if (!n) break;
+        p = n->key->path;
+        eph_unlink(*s, *n);
+      }
+      delete_node(p);
+    }
     // stale watch registrations for this session are skipped at fire time
     uint64_t cid = s->conn_id.load();
     if (close_conn_too && cid != 0) {
@@ -1383,40 +1561,52 @@ struct Ensemble::Impl {
 
   // ---------------- watches (shard lock held) ----------------
 
-  void fire_data_watches_locked(Shard& sh, const std::string& path, int32_t event_type) {
-    auto it = sh.data_watches.find(path);
+  // the watcher set for `ref`, created on first use
+  static std::set<int64_t>& watch_set(WatchMap& m, const PathRef& ref) {
+    auto it = m.find(ref);
+    if (it == m.end()) it = m.emplace(PathKey{std::string(ref.path), ref.hash}, std::set<int64_t>()).first;
+    return it->second;
+  }
+
+  // A shard with no watches at all (the registration hot path) skips the
+  // probes.
+  void fire_data_watches_locked(Shard& sh, const PathRef& ref, int32_t event_type) {
+    if (sh.data_watches.empty()) return;
+    auto it = sh.data_watches.find(ref);
     if (it == sh.data_watches.end()) return;
     std::set<int64_t> watchers = std::move(it->second);
     sh.data_watches.erase(it);
-    deliver_watch(watchers, path, event_type);
+    deliver_watch(watchers, ref.path, event_type);
   }
 
-  void fire_child_watches_locked(Shard& sh, const std::string& path) {
-    auto it = sh.child_watches.find(path);
+  void fire_child_watches_locked(Shard& sh, const PathRef& ref) {
+    if (sh.child_watches.empty()) return;
+    auto it = sh.child_watches.find(ref);
     if (it == sh.child_watches.end()) return;
     std::set<int64_t> watchers = std::move(it->second);
     sh.child_watches.erase(it);
-    deliver_watch(watchers, path, kEventNodeChildrenChanged);
+    deliver_watch(watchers, ref.path, kEventNodeChildrenChanged);
   }
 
   // NodeDeleted goes to data watchers AND child watchers of the deleted
   // node, deduplicated per session — ZooKeeper's DataTree passes the
   // already-triggered set to the child-watch trigger so a session holding
   // both watch kinds gets ONE event
-  void fire_deleted_watches_locked(Shard& sh, const std::string& path) {
+  void fire_deleted_watches_locked(Shard& sh, const PathRef& ref) {
+    if (sh.data_watches.empty() && sh.child_watches.empty()) return;
     std::set<int64_t> watchers;
-    if (auto it = sh.data_watches.find(path); it != sh.data_watches.end()) {
+    if (auto it = sh.data_watches.find(ref); it != sh.data_watches.end()) {
       watchers = std::move(it->second);
       sh.data_watches.erase(it);
     }
-    if (auto it = sh.child_watches.find(path); it != sh.child_watches.end()) {
+    if (auto it = sh.child_watches.find(ref); it != sh.child_watches.end()) {
       watchers.insert(it->second.begin(), it->second.end());
       sh.child_watches.erase(it);
     }
-    if (!watchers.empty()) deliver_watch(watchers, path, kEventNodeDeleted);
+    if (!watchers.empty()) deliver_watch(watchers, ref.path, kEventNodeDeleted);
   }
 
-  void deliver_watch(const std::set<int64_t>& watchers, const std::string& path, int32_t event_type) {
+  void deliver_watch(const std::set<int64_t>& watchers, std::string_view path, int32_t event_type) {
     for (int64_t sid : watchers) {
       uint64_t cid = 0;
       {
@@ -1439,7 +1629,7 @@ struct Ensemble::Impl {
       WatcherEvent ev;
       ev.type = event_type;
       ev.state = kStateSyncConnected;
-      ev.path = path;
+      ev.path = std::string(path);
       ev.serialize(w);
       frame_packet(&pkt);
       send_packet(cp.get(), std::move(pkt));
@@ -1450,30 +1640,28 @@ struct Ensemble::Impl {
 
   template <typename BodyFn>
   void send_reply(Conn* c, int32_t xid, int64_t zxid, int32_t err, BodyFn body) {
-    // fast path: serialize straight into the connection's output buffer (one
-    // allocation-free append per reply, flushed once per event drain)
-    if (latency_ms.load(std::memory_order_relaxed) == 0 && loops[c->io_idx]->on_loop_thread()) {
-      {
-        std::lock_guard<std::mutex> og(c->out_mu);
-        if (c->dead.load(std::memory_order_relaxed)) return;
-        size_t start = c->outbuf.size();
-        c->outbuf.append(4, '\0');
-        JuteWriter w(&c->outbuf);
-        ReplyHeader hdr;
-        hdr.xid = xid;
-        hdr.zxid = zxid;
-        hdr.err = err;
-        hdr.serialize(w);
-        if constexpr (!std::is_same_v<BodyFn, std::nullptr_t>) {
-          if (err == kZOk) body(w);
-        }
-        uint32_t n = static_cast<uint32_t>(c->outbuf.size() - start - 4);
-        c->outbuf[start] = static_cast<char>(n >> 24);
-        c->outbuf[start + 1] = static_cast<char>(n >> 16);
-        c->outbuf[start + 2] = static_cast<char>(n >> 8);
-        c->outbuf[start + 3] = static_cast<char>(n);
+    // fast path (handlers run on the owner loop inside a drain): serialize
+    // straight into the connection's staging buffer — no lock, no allocation,
+    // no timer; the flush that ends the drain moves it to outbuf once
+    if (c->draining && latency_ms.load(std::memory_order_relaxed) == 0) {
+      if (c->dead.load(std::memory_order_relaxed)) return;
+      size_t start = c->stage.size();
+      c->stage.append(4, '\0');
+      JuteWriter w(&c->stage);
+      ReplyHeader hdr;
+      hdr.xid = xid;
+      hdr.zxid = zxid;
+      hdr.err = err;
+      hdr.serialize(w);
+      if constexpr (!std::is_same_v<BodyFn, std::nullptr_t>) {
+        if (err == kZOk) body(w);
       }
-      ensure_flush_scheduled(c);
+      uint32_t n = static_cast<uint32_t>(c->stage.size() - start - 4);
+      c->stage[start] = static_cast<char>(n >> 24);
+      c->stage[start + 1] = static_cast<char>(n >> 16);
+      c->stage[start + 2] = static_cast<char>(n >> 8);
+      c->stage[start + 3] = static_cast<char>(n);
+      c->stage_pub.store(c->stage.size(), std::memory_order_release);
       return;
     }
     std::string pkt;
@@ -1524,9 +1712,18 @@ struct Ensemble::Impl {
       return;
     }
     if (loops[c->io_idx]->on_loop_thread()) {
-      // reply path: queue only; flushed once per event drain (on_conn_event)
-      // with a same-iteration 0 ms timer as the safety net for sends outside
-      // the event path (sweep-timer watch deliveries)
+      if (c->draining) {
+        // the connection being drained right now (multi / connect replies,
+        // watch events its own request fired): stage behind the replies
+        // already staged, so per-connection order is generation order
+        if (c->dead.load()) return;
+        c->stage += pkt;
+        c->stage_pub.store(c->stage.size(), std::memory_order_release);
+        return;
+      }
+      // another connection of this loop: queue only; flushed by a
+      // same-iteration 0 ms timer (also the safety net for sends outside the
+      // event path, e.g. sweep-timer watch deliveries)
       {
         std::lock_guard<std::mutex> og(c->out_mu);
         if (c->dead.load()) return;
@@ -1556,6 +1753,16 @@ struct Ensemble::Impl {
   void deliver(Conn* c, std::string pkt) {
     std::lock_guard<std::mutex> og(c->out_mu);
     if (c->dead.load()) return;
+    if (c->draining && !loops[c->io_idx]->on_loop_thread()) {
+      // The owner loop is mid-drain with replies staged outside this lock.
+      // Record the stage position this packet arrived at; the drain's flush
+      // interleaves it there. That is where a locked append would have put
+      // it: a reply the owner stages after taking a shard lock we released
+      // (e.g. a read of data whose watch we are delivering) is published
+      // after this load and so stays behind the event.
+      c->xq.emplace_back(c->stage_pub.load(std::memory_order_acquire), std::move(pkt));
+      return;
+    }
     if (c->outbuf.empty()) {
       size_t off = 0;
       while (off < pkt.size()) {
@@ -1600,10 +1807,36 @@ struct Ensemble::Impl {
     });
   }
 
-  void flush_out(Conn* c) {
+  // end_drain: the owner loop finished a drain — move the staged replies
+  // (and whatever other threads delivered meanwhile, at their recorded
+  // positions) into outbuf under the one lock this flush takes anyway.
+  void flush_out(Conn* c, bool end_drain = false) {
     bool close_now = false;
     {
       std::lock_guard<std::mutex> og(c->out_mu);
+      if (end_drain) {
+        c->draining = false;
+        if (c->xq.empty()) {
+          if (c->outbuf.empty())
+            c->outbuf.swap(c->stage);  // steady state: buffers trade places, no copy
+          else
+            c->outbuf += c->stage;
+        } else {
+          size_t pos = 0;
+          for (auto& x : c->xq) {
+            size_t at = std::min(x.first, c->stage.size());
+            if (at > pos) {
+              c->outbuf.append(c->stage, pos, at - pos);
+              pos = at;
+            }
+            c->outbuf += x.second;
+          }
+          c->outbuf.append(c->stage, pos, std::string::npos);
+          c->xq.clear();
+        }
+        c->stage.clear();
+        c->stage_pub.store(0, std::memory_order_relaxed);
+      }
       size_t off = 0;
       while (off < c->outbuf.size()) {
         ssize_t n = send(c->fd, c->outbuf.data() + off, c->outbuf.size() - off, MSG_NOSIGNAL);
@@ -1805,10 +2038,11 @@ void Ensemble::expire_session(int64_t session_id) { impl_->kill_session(session_
 void Ensemble::set_latency_ms(int ms) { impl_->latency_ms.store(ms); }
 
 NodeInfo Ensemble::get(const std::string& path) const {
-  auto& sh = impl_->shard_of(path);
+  PathRef ref = ref_of(path);
+  auto& sh = impl_->shard_of(ref);
   std::lock_guard<std::mutex> g(sh.mu);
   NodeInfo info;
-  auto it = sh.nodes.find(path);
+  auto it = sh.nodes.find(ref);
   if (it != sh.nodes.end()) {
     info.exists = true;
     info.data = it->second.data;
@@ -1819,14 +2053,11 @@ NodeInfo Ensemble::get(const std::string& path) const {
 
 std::vector<std::string> Ensemble::children(const std::string& path) const {
   std::vector<std::string> out;
-  {
-    auto& sh = impl_->shard_of(path);
-    std::lock_guard<std::mutex> g(sh.mu);
-    auto it = sh.nodes.find(path);
-    if (it == sh.nodes.end()) return out;
-    out.assign(it->second.children.begin(), it->second.children.end());
-  }
-  std::sort(out.begin(), out.end());
+  PathRef ref = ref_of(path);
+  auto& sh = impl_->shard_of(ref);
+  std::lock_guard<std::mutex> g(sh.mu);
+  auto it = sh.nodes.find(ref);
+  if (it != sh.nodes.end()) Impl::list_children(it->second, &out);
   return out;
 }
 
@@ -1848,7 +2079,7 @@ size_t Ensemble::ephemeral_count() const {
   size_t n = 0;
   for (const auto& s : snap) {
     std::lock_guard<std::mutex> eg(s->eph_mu);
-    n += s->ephemerals.size();
+    n += s->eph_count;
   }
   return n;
 }
@@ -1864,17 +2095,18 @@ int64_t Ensemble::zxid() const { return impl_->zxid_counter.load(); }
 
 std::map<std::string, uint64_t> Ensemble::counters() const {
   std::map<std::string, uint64_t> out;
-  const auto& o = impl_->ops;
-  out["connect"] = o.connect.load();
-  out["create"] = o.create.load();
-  out["delete"] = o.del.load();
-  out["exists"] = o.exists.load();
-  out["getData"] = o.get_data.load();
-  out["setData"] = o.set_data.load();
-  out["getChildren"] = o.get_children.load();
-  out["ping"] = o.ping.load();
-  out["closeSession"] = o.close_session.load();
-  out["unknown"] = o.unknown.load();
+  for (const auto& o : impl_->ops) {  // sum over the per-loop blocks
+    out["connect"] += o.connect.load();
+    out["create"] += o.create.load();
+    out["delete"] += o.del.load();
+    out["exists"] += o.exists.load();
+    out["getData"] += o.get_data.load();
+    out["setData"] += o.set_data.load();
+    out["getChildren"] += o.get_children.load();
+    out["ping"] += o.ping.load();
+    out["closeSession"] += o.close_session.load();
+    out["unknown"] += o.unknown.load();
+  }
   for (auto it = out.begin(); it != out.end();) {
     if (it->second == 0)
       it = out.erase(it);

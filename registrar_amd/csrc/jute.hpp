@@ -22,6 +22,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <string_view>
 #include <vector>
 
 namespace registrar {
@@ -157,12 +158,12 @@ class JuteWriter {
 
   void write_bool(bool v) { out_->push_back(v ? 1 : 0); }
 
-  void write_string(const std::string& s) {
+  void write_string(std::string_view s) {
     write_int(static_cast<int32_t>(s.size()));
-    out_->append(s);
+    out_->append(s.data(), s.size());
   }
 
-  void write_buffer(const std::string& s) { write_string(s); }
+  void write_buffer(std::string_view s) { write_string(s); }
 
   void write_null_buffer() { write_int(-1); }
 
@@ -209,6 +210,21 @@ class JuteReader {
   }
 
   std::string read_buffer() { return read_string(); }
+
+  // In-place reads: a view of the string/buffer bytes inside the frame (same
+  // bounds checks as read_string; null reads as empty). Valid only while the
+  // frame's storage is: the server's handlers use these on frames that live
+  // in the connection's receive buffer for the whole event drain.
+  std::string_view read_string_view() {
+    int32_t n = read_int();
+    if (n < 0) return std::string_view();
+    need(static_cast<size_t>(n));
+    std::string_view s(data_ + pos_, static_cast<size_t>(n));
+    pos_ += static_cast<size_t>(n);
+    return s;
+  }
+
+  std::string_view read_buffer_view() { return read_string_view(); }
 
   // Validate-and-skip a length-prefixed string without materializing it
   // (hot-path requests carry ACL scheme/id strings the server discards).

@@ -15,11 +15,13 @@
 
 #include <atomic>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <functional>
 #include <map>
 #include <mutex>
+#include <new>
 #include <queue>
 #include <stdexcept>
 #include <thread>
@@ -40,6 +42,51 @@ inline int64_t now_us() {
   clock_gettime(CLOCK_MONOTONIC, &ts);
   return static_cast<int64_t>(ts.tv_sec) * 1000000 + ts.tv_nsec / 1000;
 }
+
+// Socket receive buffer: read() lands directly in its tail (no bounce buffer,
+// no append), frames are parsed in place between begin and end. Bytes only
+// move inside tail() — compaction or growth before the next read — never
+// while a caller is looking at consumed-but-not-yet-released frames, so
+// pointers handed out by ptr() stay valid until the next tail() call.
+class RecvBuf {
+ public:
+  RecvBuf() = default;
+  ~RecvBuf() { free(data_); }
+  RecvBuf(const RecvBuf&) = delete;
+  RecvBuf& operator=(const RecvBuf&) = delete;
+
+  size_t size() const { return end_ - begin_; }
+  const char* ptr() const { return data_ + begin_; }
+  void consume(size_t n) { begin_ += n; }
+  void clear() { begin_ = end_ = 0; }
+
+  // Make at least min_free writable bytes at the tail and return them;
+  // *free_out is how many there are (read up to that many, then commit()).
+  char* tail(size_t min_free, size_t* free_out) {
+    if (begin_ == end_) begin_ = end_ = 0;
+    if (cap_ - end_ < min_free) {
+      if (begin_ > 0) {
+        memmove(data_, data_ + begin_, end_ - begin_);
+        end_ -= begin_;
+        begin_ = 0;
+      }
+      if (cap_ - end_ < min_free) {
+        size_t ncap = cap_ * 2 > end_ + min_free ? cap_ * 2 : end_ + min_free;
+        char* nd = static_cast<char*>(realloc(data_, ncap));
+        if (!nd) throw std::bad_alloc();
+        data_ = nd;
+        cap_ = ncap;
+      }
+    }
+    *free_out = cap_ - end_;
+    return data_ + end_;
+  }
+  void commit(size_t n) { end_ += n; }
+
+ private:
+  char* data_ = nullptr;
+  size_t cap_ = 0, begin_ = 0, end_ = 0;
+};
 
 class EventLoop {
  public:

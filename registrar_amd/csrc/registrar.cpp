@@ -255,9 +255,14 @@ int heartbeat_prepared(zk::ZkClient& client, PreparedRegistration& prep, const z
 RegisterResult register_prepared(zk::ZkClient& client, PreparedRegistration& prep, const Logger& log) {
   RegisterResult result;
   const RegistrationConfig& cfg = prep.cfg;
-  Logger rlog =
-      log.child({{"component", Json("register")}, {"domain", Json(cfg.domain)}, {"path", Json(prep.path)}});
-  rlog.debug("register: entered");
+  // the child logger (three bound Json fields) and every debug record's
+  // fields are built only when they will be written: at debug level, or on
+  // the error path
+  const bool dbg = log.enabled(LogLevel::Debug);
+  auto make_rlog = [&] {
+    return log.child({{"component", Json("register")}, {"domain", Json(cfg.domain)}, {"path", Json(prep.path)}});
+  };
+  if (dbg) make_rlog().debug("register: entered");
 
   size_t n_nodes = prep.nodes.size();
   size_t n_dirs = prep.dirs.size();
@@ -308,7 +313,7 @@ RegisterResult register_prepared(zk::ZkClient& client, PreparedRegistration& pre
       std::vector<std::string> datas(prep.dirs.size());
       std::vector<int> rcs = client.create_many(prep.dirs, datas, 0);
       if (!check_dirs(rcs, 0)) {
-        rlog.debug("setupDirectories: failed", {{"err", Json(result.error)}});
+        if (dbg) make_rlog().debug("setupDirectories: failed", {{"err", Json(result.error)}});
         return result;
       }
     }
@@ -345,7 +350,7 @@ RegisterResult register_prepared(zk::ZkClient& client, PreparedRegistration& pre
       if (!race || attempt >= 3) {
         result.rc = rc;
         result.error = std::string("atomicSwap: multi failed: ") + zk::error_name(rc);
-        rlog.debug("atomicSwap: failed", {{"err", Json(result.error)}});
+        if (dbg) make_rlog().debug("atomicSwap: failed", {{"err", Json(result.error)}});
         return result;
       }
       // another session created/removed one of our nodes between the read
@@ -357,13 +362,13 @@ RegisterResult register_prepared(zk::ZkClient& client, PreparedRegistration& pre
     // in one pipelined round trip
     std::vector<int> rcs = client.delete_many(prep.nodes);
     if (!check_cleanup(rcs, 0)) {
-      rlog.debug("cleanupPreviousEntries: failed", {{"err", Json(result.error)}});
+      if (dbg) make_rlog().debug("cleanupPreviousEntries: failed", {{"err", Json(result.error)}});
       return result;
     }
     std::this_thread::sleep_for(std::chrono::milliseconds(cfg.settle_ms));
     std::vector<int> rcs2 = client.submit_template(prep.rest_tpl);
     if (!check_dirs(rcs2, 0) || !check_creates(rcs2, n_dirs)) {
-      rlog.debug("register: failed", {{"err", Json(result.error)}});
+      if (dbg) make_rlog().debug("register: failed", {{"err", Json(result.error)}});
       return result;
     }
   } else {
@@ -372,7 +377,7 @@ RegisterResult register_prepared(zk::ZkClient& client, PreparedRegistration& pre
     // guarantees the same final state as the reference's staged barriers
     std::vector<int> rcs = client.submit_template(prep.register_tpl);
     if (!check_cleanup(rcs, 0) || !check_dirs(rcs, n_nodes) || !check_creates(rcs, n_nodes + n_dirs)) {
-      rlog.debug("register: failed", {{"err", Json(result.error)}});
+      if (dbg) make_rlog().debug("register: failed", {{"err", Json(result.error)}});
       return result;
     }
   }
@@ -386,20 +391,20 @@ RegisterResult register_prepared(zk::ZkClient& client, PreparedRegistration& pre
     if (rc != zk::kZOk) {
       result.rc = rc;
       result.error = std::string("registerService: put ") + prep.path + " failed: " + zk::error_name(rc);
-      rlog.error("registerService: put failed", {{"err", Json(result.error)}});
+      make_rlog().error("registerService: put failed", {{"err", Json(result.error)}});
       result.znodes.clear();
       return result;
     }
     if (std::find(result.znodes.begin(), result.znodes.end(), prep.path) == result.znodes.end())
       result.znodes.push_back(prep.path);
-    rlog.debug("registerService: done");
+    if (dbg) make_rlog().debug("registerService: done");
   }
 
   result.rc = zk::kZOk;
-  {
+  if (dbg) {
     Json zn = Json::array();
     for (const auto& n : result.znodes) zn.push_back(Json(n));
-    rlog.debug("register: done", {{"znodes", std::move(zn)}});
+    make_rlog().debug("register: done", {{"znodes", std::move(zn)}});
   }
   return result;
 }

@@ -48,12 +48,49 @@ void set_nodelay(int fd) {
 struct ZkClient::Impl {
   enum class Phase { Idle, TcpConnecting, Handshaking, Ready, Stopped };
 
+  // Completion of a whole pre-serialized batch: lives on the submitting
+  // caller's stack; signalled once, after the last reply (or on failure).
+  struct BatchWaiter {
+    std::mutex mu;
+    std::condition_variable cv;
+    bool done = false;
+    void signal() {
+      // notify under the lock: the waiter's stack frame may go away the
+      // moment it can re-take mu
+      std::lock_guard<std::mutex> g(mu);
+      done = true;
+      cv.notify_all();
+    }
+    void wait() {
+      std::unique_lock<std::mutex> g(mu);
+      cv.wait(g, [&] { return done; });
+    }
+  };
+
   struct Pending {
-    int32_t xid;
+    int32_t xid;  // single op: its xid; batch: the FIRST xid of the run
     int32_t op;
     // rc + body reader (null unless rc==kZOk and the op has a body)
     std::function<void(int rc, JuteReader* r)> done;
+    // batch record (submit_template): `count` consecutive xids answered in
+    // order; reply i's rc is written straight into (*rcs)[i] — no callback,
+    // no lock per reply — and the waiter is signalled once at the end
+    std::vector<int>* rcs = nullptr;
+    uint32_t count = 1;
+    uint32_t next = 0;  // replies received so far
+    BatchWaiter* waiter = nullptr;
   };
+
+  static int32_t xid_add(int32_t xid, uint32_t i) {
+    return static_cast<int32_t>(static_cast<uint32_t>(xid) + i);
+  }
+
+  // fail what is left of a batch with rc and wake its submitter
+  static void fail_batch(Pending& p, int rc) {
+    for (uint32_t i = p.next; i < p.count; i++) (*p.rcs)[i] = rc;
+    p.next = p.count;
+    p.waiter->signal();
+  }
 
   ZkClientConfig cfg;
   Logger log;
@@ -65,8 +102,7 @@ struct ZkClient::Impl {
   // ---- loop-thread-only state ----
   Phase phase = Phase::Idle;
   int fd = -1;
-  std::string inbuf;
-  size_t inpos = 0;
+  RecvBuf inbuf;
   std::string outbuf;
   bool flush_scheduled = false;
   std::deque<Pending> pending;
@@ -300,7 +336,6 @@ struct ZkClient::Impl {
       fd = -1;
     }
     inbuf.clear();
-    inpos = 0;
     outbuf.clear();
     flush_scheduled = false;
   }
@@ -308,19 +343,26 @@ struct ZkClient::Impl {
   void fail_all_pending(int rc) {
     std::deque<Pending> q;
     q.swap(pending);
-    for (auto& p : q)
-      if (p.done) p.done(rc, nullptr);
+    for (auto& p : q) {
+      if (p.rcs)
+        fail_batch(p, rc);
+      else if (p.done)
+        p.done(rc, nullptr);
+    }
   }
 
   // ---------------- frame processing ----------------
 
   bool read_frames() {
+    // read straight into the receive buffer's tail; replies are parsed in
+    // place (the buffer only moves inside tail(), before the handlers run)
     bool eof = false;
-    char buf[65536];
     while (true) {
-      ssize_t n = read(fd, buf, sizeof(buf));
+      size_t room = 0;
+      char* dst = inbuf.tail(65536, &room);
+      ssize_t n = read(fd, dst, room);
       if (n > 0) {
-        inbuf.append(buf, static_cast<size_t>(n));
+        inbuf.commit(static_cast<size_t>(n));
       } else if (n == 0) {
         // process buffered frames first: the server sends its final frames
         // (e.g. an expired-handshake ConnectResponse) right before closing
@@ -335,9 +377,9 @@ struct ZkClient::Impl {
     }
     last_recv = now_ms();
     while (true) {
-      size_t avail = inbuf.size() - inpos;
+      size_t avail = inbuf.size();
       if (avail < 4) break;
-      const unsigned char* p = reinterpret_cast<const unsigned char*>(inbuf.data() + inpos);
+      const unsigned char* p = reinterpret_cast<const unsigned char*>(inbuf.ptr());
       uint32_t len = (static_cast<uint32_t>(p[0]) << 24) | (static_cast<uint32_t>(p[1]) << 16) |
                      (static_cast<uint32_t>(p[2]) << 8) | static_cast<uint32_t>(p[3]);
       if (len > 64 * 1024 * 1024) {
@@ -346,13 +388,10 @@ struct ZkClient::Impl {
       }
       if (avail < 4 + len) break;
       // parse in place — no per-reply copy; handlers never touch inbuf
-      const char* body = inbuf.data() + inpos + 4;
-      inpos += 4 + len;
+      // (a handler that tears the socket down only resets its offsets)
+      const char* body = inbuf.ptr() + 4;
+      inbuf.consume(4 + len);
       if (!handle_frame(body, len)) return false;  // handler may reconnect/teardown
-    }
-    if (inpos > 0 && fd >= 0) {
-      inbuf.erase(0, inpos);
-      inpos = 0;
     }
     if (eof) {
       // a handler may already have torn the socket down (expiry path)
@@ -456,6 +495,28 @@ struct ZkClient::Impl {
         on_connection_lost("unexpected reply");
         return false;
       }
+      if (pending.front().rcs) {
+        // batch record: replies arrive in xid order; write the rc in place
+        // and complete the batch as a unit at its last reply
+        Pending& bp = pending.front();
+        int32_t want = xid_add(bp.xid, bp.next);
+        if (want != hdr.xid) {
+          log.error("zookeeper: xid mismatch", {{"expected", Json(static_cast<int64_t>(want))},
+                                                {"got", Json(static_cast<int64_t>(hdr.xid))}});
+          Pending failed = std::move(bp);
+          pending.pop_front();
+          fail_batch(failed, kZConnectionLoss);
+          on_connection_lost("xid mismatch");
+          return false;
+        }
+        (*bp.rcs)[bp.next++] = hdr.err;
+        if (bp.next == bp.count) {
+          BatchWaiter* wtr = bp.waiter;
+          pending.pop_front();
+          wtr->signal();
+        }
+        return true;
+      }
       Pending p = std::move(pending.front());
       pending.pop_front();
       if (p.xid != hdr.xid) {
@@ -518,7 +579,11 @@ struct ZkClient::Impl {
     outbuf[start + 1] = static_cast<char>(n >> 16);
     outbuf[start + 2] = static_cast<char>(n >> 8);
     outbuf[start + 3] = static_cast<char>(n);
-    pending.push_back(Pending{xid, op, std::move(done)});
+    Pending p;
+    p.xid = xid;
+    p.op = op;
+    p.done = std::move(done);
+    pending.push_back(std::move(p));
     schedule_flush();
   }
 
@@ -1132,32 +1197,39 @@ std::vector<int> ZkClient::submit_template(BatchTemplate& t) {
   size_t n = t.xid_offsets.size();
   std::vector<int> rcs(n, kZConnectionLoss);
   if (n == 0) return rcs;
-  BatchState st;
-  st.total = n;
-  st.rcs = &rcs;
-  BatchState* stp = &st;
-  impl_->loop.post([this, &t, stp, n] {
+  Impl::BatchWaiter waiter;
+  Impl::BatchWaiter* wp = &waiter;
+  std::vector<int>* rp = &rcs;
+  impl_->loop.post([this, &t, wp, rp, n] {
     if (impl_->phase != Impl::Phase::Ready) {
-      for (size_t i = 0; i < n; i++)
-        stp->complete(i, impl_->phase == Impl::Phase::Stopped ? kZSessionExpired : kZConnectionLoss);
+      int rc = impl_->phase == Impl::Phase::Stopped ? kZSessionExpired : kZConnectionLoss;
+      for (size_t i = 0; i < n; i++) (*rp)[i] = rc;
+      wp->signal();
       return;
     }
-    // patch fresh xids in place, register pendings, append the whole stream
+    // patch fresh (consecutive) xids in place, register ONE pending record
+    // for the whole run, append the whole stream
+    int32_t first = impl_->next_xid;
     for (size_t i = 0; i < n; i++) {
-      int32_t xid = impl_->next_xid++;
+      uint32_t u = static_cast<uint32_t>(Impl::xid_add(first, static_cast<uint32_t>(i)));
       size_t off = t.xid_offsets[i];
-      uint32_t u = static_cast<uint32_t>(xid);
       t.buf[off] = static_cast<char>(u >> 24);
       t.buf[off + 1] = static_cast<char>(u >> 16);
       t.buf[off + 2] = static_cast<char>(u >> 8);
       t.buf[off + 3] = static_cast<char>(u);
-      impl_->pending.push_back(
-          Impl::Pending{xid, t.ops[i], [stp, i](int rc, JuteReader*) { stp->complete(i, rc); }});
     }
+    impl_->next_xid = Impl::xid_add(first, static_cast<uint32_t>(n));
+    Impl::Pending p;
+    p.xid = first;
+    p.op = t.ops[0];
+    p.rcs = rp;
+    p.count = static_cast<uint32_t>(n);
+    p.waiter = wp;
+    impl_->pending.push_back(std::move(p));
     impl_->outbuf += t.buf;
     impl_->schedule_flush();
   });
-  st.wait();
+  waiter.wait();
   return rcs;
 }
 

@@ -26,7 +26,7 @@ ext = Pybind11Extension(
     # a header edit must rebuild every TU (setuptools skips unchanged .cpp
     # otherwise — a jute.hpp fix once shipped stale objects)
     depends=sorted(glob.glob(os.path.join(CSRC, "*.hpp"))),
-    cxx_std=17,
+    cxx_std=20,
     extra_compile_args=["-O2", "-g", "-Wall", "-pthread"],
     extra_link_args=["-pthread"],
 )
