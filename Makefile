@@ -9,7 +9,7 @@ CORE_SRCS := $(SRCDIR)/ensemble.cpp $(SRCDIR)/zkclient.cpp $(SRCDIR)/registrar.c
              $(SRCDIR)/health.cpp $(SRCDIR)/orchestrator.cpp $(SRCDIR)/gpu.cpp
 HDRS := $(wildcard $(SRCDIR)/*.hpp)
 
-.PHONY: all ext daemon test check clean tsan asan stress hotpath
+.PHONY: all ext daemon test check clean tsan asan stress hotpath hotpath-prof
 
 all: ext daemon
 
@@ -49,6 +49,15 @@ hotpath: $(BINDIR)/hotpath
 $(BINDIR)/hotpath: $(SRCDIR)/hotpath_main.cpp $(CORE_SRCS) $(HDRS)
 	@mkdir -p $(BINDIR)
 	$(CXX) $(CXXFLAGS) -o $@ $(SRCDIR)/hotpath_main.cpp $(CORE_SRCS)
+
+# the same tool as a sampling profiler of the ensemble IO thread: self time per
+# symbol and the commonest call chains on stderr (docs/perf_nodestore.md)
+hotpath-prof: $(BINDIR)/hotpath-prof
+
+$(BINDIR)/hotpath-prof: $(SRCDIR)/hotpath_main.cpp $(CORE_SRCS) $(HDRS)
+	@mkdir -p $(BINDIR)
+	$(CXX) $(CXXFLAGS) -DHOTPATH_PROF -rdynamic -fno-omit-frame-pointer -o $@ \
+		$(SRCDIR)/hotpath_main.cpp $(CORE_SRCS) -ldl
 
 # gcc-11's libtsan mismodels this glibc's condition_variable timed waits
 # (verified false positives on a textbook cv program), so sanitizer builds

@@ -178,7 +178,16 @@ PYBIND11_MODULE(_core, m) {
       .def("ephemeral_count", &zk::Ensemble::ephemeral_count)
       .def("session_ids", &zk::Ensemble::session_ids)
       .def("zxid", &zk::Ensemble::zxid)
-      .def("counters", &zk::Ensemble::counters);
+      .def("counters", &zk::Ensemble::counters)
+      .def_static("node_store_layout", [] {
+        zk::NodeStoreLayout l = zk::Ensemble::node_store_layout();
+        py::dict d;
+        d["shards"] = l.shards;
+        d["header_bytes"] = l.header_bytes;
+        d["max_cached_per_class"] = l.max_cached_per_class;
+        d["classes"] = l.classes;
+        return d;
+      });
 
   // ---- ZkClient ----
   py::class_<zk::ZkClient>(m, "ZkClient")

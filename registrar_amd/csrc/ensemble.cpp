@@ -67,10 +67,11 @@ bool valid_path(std::string_view p) {
   return true;
 }
 
-// Tree and watch maps are keyed by (path, hash of path). A request hashes its
-// path once: the same value picks the shard and probes the map, and lookups
-// go by view (C++20 heterogeneous lookup) so no std::string is built to find
-// a node. The map key is the one owning copy of a path.
+// The node table and the watch maps are keyed by (path, hash of path). A
+// request hashes its path once: the same value picks the shard and probes the
+// table, and lookups go by view so no std::string is built to find a node.
+// A node's path lives once, inline in the node's block (NodeStore below); the
+// watch maps own their keys (PathKey, C++20 heterogeneous lookup).
 struct PathKey {
   std::string path;
   size_t hash;
@@ -117,40 +118,238 @@ struct Ensemble::Impl {
   };
   using SessionPtr = std::shared_ptr<Session>;
 
-  // Map nodes are address-stable, so the tree links nodes by pointer:
-  //   - key points at the node's own map key (its path; immutable),
+  // A znode is ONE block: this header, then its path bytes, then its data
+  // bytes. Blocks never move, so the tree links nodes by pointer:
+  //   - hash / chain / path_len are the node's place in its shard's table
+  //     (shard lock); the path is immutable,
   //   - first_child / nchildren and the children's parent / sib_prev /
   //     sib_next are guarded by THIS node's shard lock (a child is only ever
   //     created or removed with its parent's shard locked, and a node with
   //     children cannot be removed),
   //   - owner / eph_prev / eph_next / eph_linked are guarded by the owner
-  //     session's eph_mu (taken inside the shard locks: shard → eph_mu).
+  //     session's eph_mu (taken inside the shard locks: shard → eph_mu),
+  //   - data lives inline behind the path while it fits the block; a setData
+  //     that outgrows the block moves it to `ext`, a buffer this node owns
+  //     (the node itself stays where it is).
   struct ZNode {
-    std::string data;
     Stat stat;
-    const PathKey* key = nullptr;
+    uint64_t hash = 0;       // full hash of the path
+    ZNode* chain = nullptr;  // next node in the bucket
     ZNode* parent = nullptr;
     ZNode* first_child = nullptr;
     ZNode* sib_prev = nullptr;
     ZNode* sib_next = nullptr;
-    int32_t nchildren = 0;
     SessionPtr owner;  // ephemeral owner (null for persistent nodes)
     ZNode* eph_prev = nullptr;
     ZNode* eph_next = nullptr;
+    char* ext = nullptr;     // out-of-line data, null while the data is inline
+    uint32_t path_len = 0;
+    uint32_t data_len = 0;
+    uint32_t inline_cap = 0;  // bytes behind the header (path + inline data)
+    uint32_t ext_cap = 0;
+    int32_t nchildren = 0;
+    uint8_t size_class = 0;  // kNoClass: block was sized exactly, never cached
     bool eph_linked = false;
 
+    char* tail() { return reinterpret_cast<char*>(this) + sizeof(ZNode); }
+    const char* tail() const { return reinterpret_cast<const char*>(this) + sizeof(ZNode); }
+    std::string_view path() const { return {tail(), path_len}; }
+    PathRef ref() const { return {path(), static_cast<size_t>(hash)}; }
+    std::string_view data() const { return {ext ? ext : tail() + path_len, data_len}; }
     std::string_view name() const {
-      std::string_view p = key->path;
+      std::string_view p = path();
       return p.substr(p.rfind('/') + 1);
+    }
+
+    void set_data(std::string_view d) {
+      if (d.size() <= inline_cap - path_len) {
+        if (ext) {
+          ::operator delete(ext);
+          ext = nullptr;
+          ext_cap = 0;
+        }
+        if (!d.empty()) memcpy(tail() + path_len, d.data(), d.size());
+      } else {
+        if (d.size() > ext_cap) {
+          char* nb = static_cast<char*>(::operator new(d.size()));
+          if (ext) ::operator delete(ext);
+          ext = nb;
+          ext_cap = static_cast<uint32_t>(d.size());
+        }
+        memcpy(ext, d.data(), d.size());
+      }
+      data_len = static_cast<uint32_t>(d.size());
     }
   };
 
-  using NodeMap = std::unordered_map<PathKey, ZNode, PathHash, PathEq>;
+  // Block size classes (header + path + data, rounded up). The registrar's
+  // own nodes (a ~25-byte path, a ~100-byte JSON record) land in the second.
+  static constexpr size_t kBlockClasses[] = {256, 384, 512, 768, 1024, 1536, 2048, 4096};
+  static constexpr size_t kNumClasses = sizeof(kBlockClasses) / sizeof(kBlockClasses[0]);
+  static constexpr uint8_t kNoClass = 0xFF;
+  // Most released blocks a shard keeps per class. A re-register cycle at 8
+  // ranks x 1000 nodes frees, then re-creates, ~125 blocks per shard at
+  // uniform hashing; 256 covers that with room for skew. Retained at most:
+  // 64 shards x 256 x 384 bytes = ~6 MB for the class the registrar uses
+  // (~174 MB only if every class of every shard fills).
+  static constexpr size_t kMaxCachedPerClass = 256;
+  static_assert(sizeof(ZNode) < kBlockClasses[0], "smallest class must hold a header");
+
   using WatchMap = std::unordered_map<PathKey, std::set<int64_t>, PathHash, PathEq>;
+
+  // One shard's nodes: an intrusive chained hash table (power-of-two bucket
+  // array of ZNode*, the chain link and the full hash live in the node) plus
+  // the shard's free lists of released blocks. Everything here is guarded by
+  // the shard's mutex. Growth relinks nodes and never moves them.
+  struct NodeStore {
+    ZNode** buckets = nullptr;
+    size_t nbuckets = 0;  // power of two
+    size_t count = 0;
+
+    // INVARIANT: a block goes onto a free list only after its node has left
+    // the hash chain, its parent's sibling list and its owner's ephemeral
+    // list (release() asserts the last two; erase() does the first), and no
+    // ZNode* is dereferenced outside the lock that guards the link it was
+    // read through. A recycled block is worse than a freed one: a stale
+    // pointer would read a live, different node and no sanitizer would see it.
+    struct FreeBlock {
+      FreeBlock* next;
+    };
+    FreeBlock* free_head[kNumClasses] = {};
+    size_t free_count[kNumClasses] = {};
+    size_t cached = 0;  // sum of free_count
+
+    NodeStore() = default;
+    NodeStore(const NodeStore&) = delete;
+    NodeStore& operator=(const NodeStore&) = delete;
+
+    ~NodeStore() {
+      for (size_t b = 0; b < nbuckets; b++) {
+        for (ZNode* n = buckets[b]; n;) {
+          ZNode* next = n->chain;
+          if (n->ext) ::operator delete(n->ext);
+          n->~ZNode();
+          ::operator delete(n);
+          n = next;
+        }
+      }
+      ::operator delete(buckets);
+      for (size_t c = 0; c < kNumClasses; c++) {
+        for (FreeBlock* f = free_head[c]; f;) {
+          FreeBlock* next = f->next;
+          ::operator delete(f);
+          f = next;
+        }
+      }
+    }
+
+    size_t size() const { return count; }
+
+    // The shard index is hash % kShards (the low 6 bits), so the bucket index
+    // takes its bits from further up.
+    size_t bucket_of(uint64_t h) const { return (h >> 8) & (nbuckets - 1); }
+
+    ZNode* find(const PathRef& r) const {
+      if (nbuckets == 0) return nullptr;
+      for (ZNode* n = buckets[bucket_of(r.hash)]; n; n = n->chain) {
+        // the stored hash settles nearly every chain step without touching
+        // the path bytes
+        if (n->hash == r.hash && n->path_len == r.path.size() &&
+            memcmp(n->tail(), r.path.data(), r.path.size()) == 0)
+          return n;
+      }
+      return nullptr;
+    }
+
+    void grow() {
+      size_t nn = nbuckets ? nbuckets * 2 : 16;
+      ZNode** nb = static_cast<ZNode**>(::operator new(nn * sizeof(ZNode*)));
+      memset(nb, 0, nn * sizeof(ZNode*));
+      ZNode** old = buckets;
+      size_t on = nbuckets;
+      buckets = nb;
+      nbuckets = nn;
+      for (size_t b = 0; b < on; b++) {
+        for (ZNode* n = old[b]; n;) {
+          ZNode* next = n->chain;
+          size_t i = bucket_of(n->hash);
+          n->chain = buckets[i];
+          buckets[i] = n;
+          n = next;
+        }
+      }
+      ::operator delete(old);
+    }
+
+    static uint8_t class_for(size_t bytes) {
+      for (size_t c = 0; c < kNumClasses; c++)
+        if (bytes <= kBlockClasses[c]) return static_cast<uint8_t>(c);
+      return kNoClass;
+    }
+
+    // A new node for r (which must not be in the table) holding `data`:
+    // exactly one block, from the free list of its class when there is one.
+    ZNode* create(const PathRef& r, std::string_view data) {
+      if (count >= nbuckets) grow();
+      size_t need = sizeof(ZNode) + r.path.size() + data.size();
+      uint8_t cls = class_for(need);
+      size_t bytes = cls == kNoClass ? need : kBlockClasses[cls];
+      void* mem;
+      if (cls != kNoClass && free_head[cls]) {
+        FreeBlock* f = free_head[cls];
+        free_head[cls] = f->next;
+        free_count[cls]--;
+        cached--;
+        mem = f;
+      } else {
+        mem = ::operator new(bytes);
+      }
+      ZNode* n = new (mem) ZNode();
+      n->hash = r.hash;
+      n->size_class = cls;
+      n->path_len = static_cast<uint32_t>(r.path.size());
+      n->inline_cap = static_cast<uint32_t>(bytes - sizeof(ZNode));
+      n->data_len = static_cast<uint32_t>(data.size());
+      memcpy(n->tail(), r.path.data(), r.path.size());
+      if (!data.empty()) memcpy(n->tail() + r.path.size(), data.data(), data.size());
+      size_t i = bucket_of(r.hash);
+      n->chain = buckets[i];
+      buckets[i] = n;
+      count++;
+      return n;
+    }
+
+    // Take n out of the table and release its block (and its out-of-line
+    // data). The caller has already unlinked it from its parent and from its
+    // owner's ephemeral list — see the invariant above.
+    void erase(ZNode* n) {
+      ZNode** pp = &buckets[bucket_of(n->hash)];
+      while (*pp != n) pp = &(*pp)->chain;
+      *pp = n->chain;
+      count--;
+      release(n);
+    }
+
+    void release(ZNode* n) {
+      if (n->parent || n->eph_linked || n->first_child) std::abort();  // invariant
+      if (n->ext) ::operator delete(n->ext);
+      uint8_t cls = n->size_class;
+      n->~ZNode();  // drops the owner reference
+      if (cls != kNoClass && free_count[cls] < kMaxCachedPerClass) {
+        FreeBlock* f = reinterpret_cast<FreeBlock*>(n);
+        f->next = free_head[cls];
+        free_head[cls] = f;
+        free_count[cls]++;
+        cached++;
+      } else {
+        ::operator delete(n);
+      }
+    }
+  };
 
   struct Shard {
     std::mutex mu;
-    NodeMap nodes;
+    NodeStore nodes;
     WatchMap data_watches;
     WatchMap child_watches;
   };
@@ -172,13 +371,14 @@ struct Ensemble::Impl {
     int64_t drain_mono_ms = 0;
     int64_t drain_wall_ms = 0;
     PathRef last_parent{std::string_view(), 0};
+    std::string scratch;  // variable-size replies are built here, then staged
     // replies produced during a drain are staged here without a lock and
     // move to outbuf once, at the flush that ends the drain
-    std::string stage;
+    ByteBuf stage;
     std::atomic<size_t> stage_pub{0};  // stage.size() after the last whole packet
     // shared output state (out_mu):
     std::mutex out_mu;
-    std::string outbuf;
+    ByteBuf outbuf;
     // true while the owner loop is inside a drain (written under out_mu by
     // the owner; the owner may read it without the lock)
     bool draining = false;
@@ -241,7 +441,7 @@ struct Ensemble::Impl {
     log.set_level(cfg.log_level);
     latency_ms.store(cfg.latency_ms);
     PathRef root = ref_of("/");
-    emplace_node(shards[root.hash % kShards], root);
+    shards[root.hash % kShards].nodes.create(root, std::string_view());
   }
 
   Shard& shard_of(const PathRef& r) { return shards[r.hash % kShards]; }
@@ -269,21 +469,7 @@ struct Ensemble::Impl {
   // ---------------- tree primitives (shard locks held) ----------------
 
   // the node at r in whichever shard r hashes to, or null
-  ZNode* find_node(const PathRef& r) {
-    Shard& sh = shard_of(r);
-    auto it = sh.nodes.find(r);
-    return it == sh.nodes.end() ? nullptr : &it->second;
-  }
-
-  // r must not exist in sh; the key string built here is the path's one
-  // owning copy
-  ZNode& emplace_node(Shard& sh, const PathRef& r) {
-    auto res = sh.nodes.emplace(std::piecewise_construct,
-                                std::forward_as_tuple(PathKey{std::string(r.path), r.hash}),
-                                std::forward_as_tuple());
-    res.first->second.key = &res.first->first;
-    return res.first->second;
-  }
+  ZNode* find_node(const PathRef& r) { return shard_of(r).nodes.find(r); }
 
   static void link_child(ZNode& par, ZNode& ch) {
     ch.parent = &par;
@@ -339,19 +525,20 @@ struct Ensemble::Impl {
 
   // Take a node that is about to be erased out of its owner's ephemeral
   // index. Runs inside the node's shard lock, BEFORE the erase: the index
-  // holds node pointers, so a node must never be freed while linked.
+  // holds node pointers, so a node must never be freed (or, worse, recycled)
+  // while linked.
   static void detach_ephemeral(ZNode& n) {
     if (!n.owner) return;
     std::lock_guard<std::mutex> eg(n.owner->eph_mu);
     eph_unlink(*n.owner, n);
   }
 
-  // Remove the node at `it` (no children; its shard csh and its parent's
-  // shard psh both locked): session index, parent link + parent Stat,
-  // watches (parent's child watch first, then NodeDeleted), erase. Returns
-  // the zxid the removal committed at.
-  int64_t remove_node_locked(Shard& csh, NodeMap::iterator it, Shard& psh) {
-    ZNode& n = it->second;
+  // Remove node n (no children; its shard csh and its parent's shard psh
+  // both locked): session index, parent link + parent Stat, watches
+  // (parent's child watch first, then NodeDeleted), erase. Returns the zxid
+  // the removal committed at.
+  int64_t remove_node_locked(Shard& csh, ZNode* np, Shard& psh) {
+    ZNode& n = *np;
     int64_t z = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
     detach_ephemeral(n);
     if (ZNode* par = n.parent) {
@@ -359,10 +546,10 @@ struct Ensemble::Impl {
       par->stat.cversion++;
       par->stat.pzxid = z;
       par->stat.num_children = par->nchildren;
-      fire_child_watches_locked(psh, ref_of(*par->key));
+      fire_child_watches_locked(psh, par->ref());
     }
-    fire_deleted_watches_locked(csh, ref_of(it->first));
-    csh.nodes.erase(it);
+    fire_deleted_watches_locked(csh, n.ref());  // n's own path bytes: before the erase
+    csh.nodes.erase(np);
     return z;
   }
 
@@ -770,13 +957,13 @@ struct Ensemble::Impl {
       PathRef pref = parent_ref(c, parent_view(path));
       TwoShardLock lk(*this, cref, pref);
       Shard& psh = *lk.second;
-      auto pit = psh.nodes.find(pref);
-      if (pit == psh.nodes.end()) {
+      ZNode* parp = psh.nodes.find(pref);
+      if (!parp) {
         err = kZNoNode;
-      } else if (pit->second.stat.ephemeral_owner != 0) {
+      } else if (parp->stat.ephemeral_owner != 0) {
         err = kZNoChildrenForEphemerals;
       } else {
-        ZNode& par = pit->second;
+        ZNode& par = *parp;
         Shard* csh = lk.first;
         std::unique_lock<std::mutex> extra;
         if (flags & kSequence) {
@@ -819,12 +1006,12 @@ struct Ensemble::Impl {
           }
           if (!owner) err = kZSessionExpired;
         }
-        if (err == kZOk && csh->nodes.find(cref) != csh->nodes.end()) err = kZNodeExists;
+        if (err == kZOk && csh->nodes.find(cref)) err = kZNodeExists;
         if (err == kZOk) {
           int64_t zz = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
           op_zxid = zz;
-          ZNode& n = emplace_node(*csh, cref);
-          n.data.assign(data.data(), data.size());
+          // one block for header, path and payload
+          ZNode& n = *csh->nodes.create(cref, data);
           n.stat.czxid = zz;
           n.stat.mzxid = zz;
           n.stat.ctime = c->drain_wall_ms;
@@ -850,10 +1037,11 @@ struct Ensemble::Impl {
     // exceed what this client actually observed — ADVICE r1). The path goes
     // out straight from the request bytes (or the SEQUENCE path).
     if (err == kZOk)
-      send_reply(c, xid, op_zxid, kZOk, [&](JuteWriter& w) {
-        w.write_string(final_path);                // CreateResponse
-        if (with_stat) created_stat.serialize(w);  // Create2Response
-      });
+      send_fixed_reply(
+          c, xid, op_zxid, 4 + final_path.size() + (with_stat ? Stat::kWireSize : 0), [&](auto& w) {
+            w.write_string(final_path);                // CreateResponse
+            if (with_stat) created_stat.serialize(w);  // Create2Response
+          });
     else
       send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), err, nullptr);
   }
@@ -871,15 +1059,15 @@ struct Ensemble::Impl {
       PathRef pref = parent_ref(c, parent_view(path));
       TwoShardLock lk(*this, cref, pref);
       Shard& csh = *lk.first;
-      auto it = csh.nodes.find(cref);
-      if (it == csh.nodes.end() || path == "/") {
+      ZNode* n = csh.nodes.find(cref);
+      if (!n || path == "/") {
         err = kZNoNode;
-      } else if (it->second.nchildren != 0) {
+      } else if (n->nchildren != 0) {
         err = kZNotEmpty;
-      } else if (version != -1 && version != it->second.stat.version) {
+      } else if (version != -1 && version != n->stat.version) {
         err = kZBadVersion;
       } else {
-        op_zxid = remove_node_locked(csh, it, *lk.second);
+        op_zxid = remove_node_locked(csh, n, *lk.second);
       }
     }
     send_reply(c, xid,
@@ -896,11 +1084,11 @@ struct Ensemble::Impl {
     PathRef pref = ref_of(parent_view(path));
     TwoShardLock lk(*this, cref, pref);
     Shard& csh = *lk.first;
-    auto it = csh.nodes.find(cref);
-    if (it == csh.nodes.end()) return false;
-    if (it->second.nchildren != 0 || it->second.parent == nullptr) return false;
-    if (only_owner && it->second.owner.get() != only_owner) return false;
-    int64_t z = remove_node_locked(csh, it, *lk.second);
+    ZNode* n = csh.nodes.find(cref);
+    if (!n) return false;
+    if (n->nchildren != 0 || n->parent == nullptr) return false;
+    if (only_owner && n->owner.get() != only_owner) return false;
+    int64_t z = remove_node_locked(csh, n, *lk.second);
     if (out_zxid) *out_zxid = z;
     return true;
   }
@@ -916,15 +1104,13 @@ struct Ensemble::Impl {
       Shard& sh = shard_of(ref);
       std::lock_guard<std::mutex> lk(sh.mu);
       if (watch) watch_set(sh.data_watches, ref).insert(sid_of(c));
-      auto it = sh.nodes.find(ref);
-      if (it == sh.nodes.end())
-        err = kZNoNode;
+      if (const ZNode* n = sh.nodes.find(ref))
+        stat = n->stat;
       else
-        stat = it->second.stat;
+        err = kZNoNode;
     }
     if (err == kZOk)
-      send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), kZOk,
-                 [&](JuteWriter& w) { stat.serialize(w); });
+      send_stat_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), stat);
     else
       send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), err, nullptr);
   }
@@ -939,13 +1125,12 @@ struct Ensemble::Impl {
       PathRef ref = ref_of(path);
       Shard& sh = shard_of(ref);
       std::lock_guard<std::mutex> lk(sh.mu);
-      auto it = sh.nodes.find(ref);
-      if (it == sh.nodes.end()) {
-        err = kZNoNode;
-      } else {
+      if (const ZNode* n = sh.nodes.find(ref)) {
         if (watch) watch_set(sh.data_watches, ref).insert(sid_of(c));
-        resp.data = it->second.data;
-        resp.stat = it->second.stat;
+        resp.data = n->data();
+        resp.stat = n->stat;
+      } else {
+        err = kZNoNode;
       }
     }
     if (err == kZOk)
@@ -967,26 +1152,25 @@ struct Ensemble::Impl {
       PathRef ref = ref_of(path);
       Shard& sh = shard_of(ref);
       std::lock_guard<std::mutex> lk(sh.mu);
-      auto it = sh.nodes.find(ref);
-      if (it == sh.nodes.end()) {
+      ZNode* n = sh.nodes.find(ref);
+      if (!n) {
         err = kZNoNode;
-      } else if (version != -1 && version != it->second.stat.version) {
+      } else if (version != -1 && version != n->stat.version) {
         err = kZBadVersion;
       } else {
         int64_t zz = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
         op_zxid = zz;
-        it->second.data.assign(data.data(), data.size());
-        it->second.stat.mzxid = zz;
-        it->second.stat.mtime = c->drain_wall_ms;
-        it->second.stat.version++;
-        it->second.stat.data_length = static_cast<int32_t>(data.size());
+        n->set_data(data);  // in place while it fits; the node never moves
+        n->stat.mzxid = zz;
+        n->stat.mtime = c->drain_wall_ms;
+        n->stat.version++;
+        n->stat.data_length = static_cast<int32_t>(data.size());
         fire_data_watches_locked(sh, ref, kEventNodeDataChanged);
-        stat = it->second.stat;
+        stat = n->stat;
       }
     }
     if (err == kZOk)
-      send_reply(c, xid, op_zxid, kZOk,
-                 [&](JuteWriter& w) { stat.serialize(w); });
+      send_stat_reply(c, xid, op_zxid, stat);
     else
       send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), err, nullptr);
   }
@@ -1001,12 +1185,11 @@ struct Ensemble::Impl {
       PathRef ref = ref_of(path);
       Shard& sh = shard_of(ref);
       std::lock_guard<std::mutex> lk(sh.mu);
-      auto it = sh.nodes.find(ref);
-      if (it == sh.nodes.end()) {
-        err = kZNoNode;
-      } else {
+      if (const ZNode* n = sh.nodes.find(ref)) {
         if (watch) watch_set(sh.child_watches, ref).insert(sid_of(c));
-        list_children(it->second, &resp.children);
+        list_children(*n, &resp.children);
+      } else {
+        err = kZNoNode;
       }
     }
     if (err == kZOk)
@@ -1028,13 +1211,12 @@ struct Ensemble::Impl {
       PathRef ref = ref_of(path);
       Shard& sh = shard_of(ref);
       std::lock_guard<std::mutex> lk(sh.mu);
-      auto it = sh.nodes.find(ref);
-      if (it == sh.nodes.end()) {
-        err = kZNoNode;
-      } else {
+      if (const ZNode* n = sh.nodes.find(ref)) {
         if (watch) watch_set(sh.child_watches, ref).insert(sid_of(c));
-        list_children(it->second, &resp.children);
-        stat = it->second.stat;
+        list_children(*n, &resp.children);
+        stat = n->stat;
+      } else {
+        err = kZNoNode;
       }
     }
     if (err == kZOk)
@@ -1245,8 +1427,7 @@ struct Ensemble::Impl {
               int64_t zz = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
               txn_zxid = zz;
               PathRef cref = ref_of(mo.path);
-              ZNode& n = emplace_node(shard_of(cref), cref);  // validated absent above
-              n.data = mo.data;
+              ZNode& n = *shard_of(cref).nodes.create(cref, mo.data);  // validated absent above
               n.stat.czxid = zz;
               n.stat.mzxid = zz;
               n.stat.ctime = c->drain_wall_ms;
@@ -1282,17 +1463,16 @@ struct Ensemble::Impl {
               txn_zxid = zz;
               PathRef cref = ref_of(mo.path);
               Shard& csh = shard_of(cref);
-              auto it = csh.nodes.find(cref);
-              if (it != csh.nodes.end()) {
+              if (ZNode* n = csh.nodes.find(cref)) {
                 // may be ANOTHER session's ephemeral: leaves its owner's index
-                detach_ephemeral(it->second);
-                if (ZNode* par = it->second.parent) {
-                  unlink_child(it->second);
+                detach_ephemeral(*n);
+                if (ZNode* par = n->parent) {
+                  unlink_child(*n);
                   par->stat.cversion++;
                   par->stat.pzxid = zz;
                   par->stat.num_children = par->nchildren;
                 }
-                csh.nodes.erase(it);
+                csh.nodes.erase(n);
               }
               data_events.push_back({mo.path, kEventNodeDeleted});
               child_events.push_back(parent);
@@ -1304,7 +1484,7 @@ struct Ensemble::Impl {
               int64_t zz = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
               txn_zxid = zz;
               if (ZNode* n = find_node(ref_of(mo.path))) {
-                n->data = mo.data;
+                n->set_data(mo.data);
                 n->stat.mzxid = zz;
                 n->stat.mtime = c->drain_wall_ms;
                 n->stat.version++;
@@ -1381,10 +1561,10 @@ struct Ensemble::Impl {
         PathRef ref = ref_of(path);
         Shard& sh = shard_of(ref);
         std::lock_guard<std::mutex> lk(sh.mu);
-        auto it = sh.nodes.find(ref);
-        if (it == sh.nodes.end())
+        const ZNode* n = sh.nodes.find(ref);
+        if (!n)
           fire_deleted = true;
-        else if (it->second.stat.mzxid > req.relative_zxid)
+        else if (n->stat.mzxid > req.relative_zxid)
           fire_changed = true;
         else
           watch_set(sh.data_watches, ref).insert(sid);
@@ -1398,8 +1578,7 @@ struct Ensemble::Impl {
         PathRef ref = ref_of(path);
         Shard& sh = shard_of(ref);
         std::lock_guard<std::mutex> lk(sh.mu);
-        auto it = sh.nodes.find(ref);
-        if (it != sh.nodes.end())
+        if (sh.nodes.find(ref))
           fire_created = true;  // appeared while the client was away
         else
           watch_set(sh.data_watches, ref).insert(sid);
@@ -1412,10 +1591,10 @@ struct Ensemble::Impl {
         PathRef ref = ref_of(path);
         Shard& sh = shard_of(ref);
         std::lock_guard<std::mutex> lk(sh.mu);
-        auto it = sh.nodes.find(ref);
-        if (it == sh.nodes.end())
+        const ZNode* n = sh.nodes.find(ref);
+        if (!n)
           fire_deleted = true;
-        else if (it->second.stat.pzxid > req.relative_zxid)
+        else if (n->stat.pzxid > req.relative_zxid)
           fire_child = true;
         else
           watch_set(sh.child_watches, ref).insert(sid);
@@ -1443,11 +1622,10 @@ struct Ensemble::Impl {
       PathRef ref = ref_of(path);
       Shard& sh = shard_of(ref);
       std::lock_guard<std::mutex> lk(sh.mu);
-      auto it = sh.nodes.find(ref);
-      if (it == sh.nodes.end())
-        err = kZNoNode;
+      if (const ZNode* n = sh.nodes.find(ref))
+        stat = n->stat;
       else
-        stat = it->second.stat;
+        err = kZNoNode;
     }
     if (err == kZOk)
       send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), kZOk, [&](JuteWriter& w) {
@@ -1468,12 +1646,11 @@ struct Ensemble::Impl {
       PathRef ref = ref_of(path);
       Shard& sh = shard_of(ref);
       std::lock_guard<std::mutex> lk(sh.mu);
-      auto it = sh.nodes.find(ref);
-      if (it == sh.nodes.end()) {
-        err = kZNoNode;
+      if (ZNode* n = sh.nodes.find(ref)) {
+        n->stat.aversion++;
+        stat = n->stat;
       } else {
-        it->second.stat.aversion++;
-        stat = it->second.stat;
+        err = kZNoNode;
       }
     }
     if (err == kZOk)
@@ -1525,7 +1702,7 @@ struct Ensemble::Impl {
         std::lock_guard<std::mutex> eg(s->eph_mu);
         ZNode* n = s->eph_head;
         if (!n) break;
-        p = n->key->path;
+        p.assign(n->path());
         eph_unlink(*s, *n);
       }
       delete_node(p);
@@ -1645,23 +1822,25 @@ struct Ensemble::Impl {
     // no timer; the flush that ends the drain moves it to outbuf once
     if (c->draining && latency_ms.load(std::memory_order_relaxed) == 0) {
       if (c->dead.load(std::memory_order_relaxed)) return;
-      size_t start = c->stage.size();
-      c->stage.append(4, '\0');
-      JuteWriter w(&c->stage);
-      ReplyHeader hdr;
-      hdr.xid = xid;
-      hdr.zxid = zxid;
-      hdr.err = err;
-      hdr.serialize(w);
-      if constexpr (!std::is_same_v<BodyFn, std::nullptr_t>) {
+      if constexpr (std::is_same_v<BodyFn, std::nullptr_t>) {
+        // header-only reply (acks and every error): fixed 20 bytes
+        stage_fixed(c, xid, zxid, err, 0, [](RawWriter&) {});
+      } else {
+        // variable-size bodies (getData, listings, ACLs): the generic writer
+        // into a scratch string, then one append
+        std::string& pkt = c->scratch;
+        begin_packet(&pkt);
+        JuteWriter w(&pkt);
+        ReplyHeader hdr;
+        hdr.xid = xid;
+        hdr.zxid = zxid;
+        hdr.err = err;
+        hdr.serialize(w);
         if (err == kZOk) body(w);
+        frame_packet(&pkt);
+        c->stage.append(pkt);
+        c->stage_pub.store(c->stage.size(), std::memory_order_release);
       }
-      uint32_t n = static_cast<uint32_t>(c->stage.size() - start - 4);
-      c->stage[start] = static_cast<char>(n >> 24);
-      c->stage[start + 1] = static_cast<char>(n >> 16);
-      c->stage[start + 2] = static_cast<char>(n >> 8);
-      c->stage[start + 3] = static_cast<char>(n);
-      c->stage_pub.store(c->stage.size(), std::memory_order_release);
       return;
     }
     std::string pkt;
@@ -1681,6 +1860,44 @@ struct Ensemble::Impl {
 
   void send_reply(Conn* c, int32_t xid, int64_t zxid, int32_t err, std::nullptr_t) {
     send_reply<std::nullptr_t>(c, xid, zxid, err, nullptr);
+  }
+
+  // Owner loop, inside a drain, no latency injection: lay one reply of known
+  // size down in the staging buffer. Room for the frame prefix, the
+  // ReplyHeader and body_size body bytes is made once; the fields go in as
+  // big-endian stores through a bump pointer. body must write exactly
+  // body_size bytes when err is OK (and is not called otherwise).
+  template <typename BodyFn>
+  void stage_fixed(Conn* c, int32_t xid, int64_t zxid, int32_t err, size_t body_size, BodyFn body) {
+    size_t n = ReplyHeader::kWireSize + (err == kZOk ? body_size : 0);
+    RawWriter w(c->stage.reserve(4 + n));
+    w.write_int(static_cast<int32_t>(n));
+    ReplyHeader hdr;
+    hdr.xid = xid;
+    hdr.zxid = zxid;
+    hdr.err = err;
+    hdr.serialize(w);
+    if (err == kZOk) body(w);
+    c->stage.commit(4 + n);
+    c->stage_pub.store(c->stage.size(), std::memory_order_release);
+  }
+
+  // An OK reply whose body has a fixed layout of body_size bytes (a Stat, a
+  // created path, both): encoded in place on the fast path; the same body
+  // function drives the generic writer everywhere else (latency injection,
+  // sends from outside a drain), so the field order lives in one place.
+  template <typename BodyFn>
+  void send_fixed_reply(Conn* c, int32_t xid, int64_t zxid, size_t body_size, BodyFn body) {
+    if (c->draining && latency_ms.load(std::memory_order_relaxed) == 0) {
+      if (c->dead.load(std::memory_order_relaxed)) return;
+      stage_fixed(c, xid, zxid, kZOk, body_size, body);
+      return;
+    }
+    send_reply(c, xid, zxid, kZOk, body);
+  }
+
+  void send_stat_reply(Conn* c, int32_t xid, int64_t zxid, const Stat& stat) {
+    send_fixed_reply(c, xid, zxid, Stat::kWireSize, [&](auto& w) { stat.serialize(w); });
   }
 
   // multi replies carry a body even on failure (per-op error results)
@@ -1717,7 +1934,7 @@ struct Ensemble::Impl {
         // watch events its own request fired): stage behind the replies
         // already staged, so per-connection order is generation order
         if (c->dead.load()) return;
-        c->stage += pkt;
+        c->stage.append(pkt);
         c->stage_pub.store(c->stage.size(), std::memory_order_release);
         return;
       }
@@ -1727,7 +1944,7 @@ struct Ensemble::Impl {
       {
         std::lock_guard<std::mutex> og(c->out_mu);
         if (c->dead.load()) return;
-        c->outbuf += pkt;
+        c->outbuf.append(pkt);
       }
       ensure_flush_scheduled(c);
       return;
@@ -1779,14 +1996,14 @@ struct Ensemble::Impl {
         }
       }
       if (off < pkt.size()) {
-        c->outbuf = pkt.substr(off);
+        c->outbuf.append(pkt.data() + off, pkt.size() - off);  // outbuf is empty here
         arm_epollout(c);
       } else if (c->closing) {
         mark_dead(c);
       }
       return;
     }
-    c->outbuf += pkt;
+    c->outbuf.append(pkt);
   }
 
   // out_mu held
@@ -1820,7 +2037,7 @@ struct Ensemble::Impl {
           if (c->outbuf.empty())
             c->outbuf.swap(c->stage);  // steady state: buffers trade places, no copy
           else
-            c->outbuf += c->stage;
+            c->outbuf.append(c->stage, 0, c->stage.size());
         } else {
           size_t pos = 0;
           for (auto& x : c->xq) {
@@ -1829,9 +2046,9 @@ struct Ensemble::Impl {
               c->outbuf.append(c->stage, pos, at - pos);
               pos = at;
             }
-            c->outbuf += x.second;
+            c->outbuf.append(x.second);
           }
-          c->outbuf.append(c->stage, pos, std::string::npos);
+          c->outbuf.append(c->stage, pos, c->stage.size() - pos);
           c->xq.clear();
         }
         c->stage.clear();
@@ -1852,7 +2069,7 @@ struct Ensemble::Impl {
         }
       }
       if (!close_now) {
-        c->outbuf.erase(0, off);
+        c->outbuf.erase_front(off);
         if (c->outbuf.empty()) {
           if (c->epollout_armed) {
             c->epollout_armed = false;
@@ -2042,11 +2259,10 @@ NodeInfo Ensemble::get(const std::string& path) const {
   auto& sh = impl_->shard_of(ref);
   std::lock_guard<std::mutex> g(sh.mu);
   NodeInfo info;
-  auto it = sh.nodes.find(ref);
-  if (it != sh.nodes.end()) {
+  if (const auto* n = sh.nodes.find(ref)) {
     info.exists = true;
-    info.data = it->second.data;
-    info.stat = it->second.stat;
+    info.data = n->data();
+    info.stat = n->stat;
   }
   return info;
 }
@@ -2056,8 +2272,7 @@ std::vector<std::string> Ensemble::children(const std::string& path) const {
   PathRef ref = ref_of(path);
   auto& sh = impl_->shard_of(ref);
   std::lock_guard<std::mutex> g(sh.mu);
-  auto it = sh.nodes.find(ref);
-  if (it != sh.nodes.end()) Impl::list_children(it->second, &out);
+  if (const auto* n = sh.nodes.find(ref)) Impl::list_children(*n, &out);
   return out;
 }
 
@@ -2113,7 +2328,22 @@ std::map<std::string, uint64_t> Ensemble::counters() const {
     else
       ++it;
   }
+  uint64_t cached = 0;
+  for (auto& sh : impl_->shards) {
+    std::lock_guard<std::mutex> g(sh.mu);
+    cached += sh.nodes.cached;
+  }
+  out["node_blocks_cached"] = cached;
   return out;
+}
+
+NodeStoreLayout Ensemble::node_store_layout() {
+  NodeStoreLayout l;
+  l.shards = Impl::kShards;
+  l.header_bytes = sizeof(Impl::ZNode);
+  l.max_cached_per_class = Impl::kMaxCachedPerClass;
+  l.classes.assign(std::begin(Impl::kBlockClasses), std::end(Impl::kBlockClasses));
+  return l;
 }
 
 }  // namespace zk

@@ -60,6 +60,16 @@ struct NodeInfo {  // introspection result
   Stat stat;
 };
 
+// Geometry of the node store (see ensemble.cpp): a znode is one block of
+// header + path + data, blocks come in size classes and each shard keeps at
+// most max_cached_per_class released blocks per class for reuse.
+struct NodeStoreLayout {
+  size_t shards = 0;
+  size_t header_bytes = 0;
+  size_t max_cached_per_class = 0;
+  std::vector<size_t> classes;  // block sizes, ascending; larger blocks are never cached
+};
+
 class Ensemble {
  public:
   explicit Ensemble(EnsembleConfig cfg);
@@ -93,8 +103,11 @@ class Ensemble {
   size_t ephemeral_count() const;
   std::vector<int64_t> session_ids() const;
   int64_t zxid() const;
-  // cumulative request counters by opcode name ("create", "exists", ...)
+  // cumulative request counters by opcode name ("create", "exists", ...),
+  // zero ones left out; plus "node_blocks_cached", the number of released
+  // node blocks the shards currently hold for reuse (always present)
   std::map<std::string, uint64_t> counters() const;
+  static NodeStoreLayout node_store_layout();
 
  private:
   struct Impl;

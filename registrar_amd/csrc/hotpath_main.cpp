@@ -20,6 +20,15 @@
 // and ZkClient::start() and are then given names (ens-io / zk-loop / caller)
 // through /proc/self/task/<tid>/comm, so the tool needs nothing from the
 // library and can be built against any revision of it.
+//
+// Built with -DHOTPATH_PROF (make hotpath-prof, which adds -rdynamic
+// -fno-omit-frame-pointer) the same program is also a sampling profiler of
+// the ensemble IO thread: ITIMER_PROF ticks, the handler keeps the samples
+// that land on that thread (PC from the ucontext plus up to four return
+// addresses found by walking frame pointers inside that thread's stack; no
+// libc calls in the handler), and at exit self time per symbol and the most
+// common 4-deep chains are printed to stderr. The timer is tick-based: run
+// enough steps for a few thousand samples.
 #include <dirent.h>
 #include <signal.h>
 #include <sys/syscall.h>
@@ -38,6 +47,19 @@
 #include "ensemble.hpp"
 #include "registrar.hpp"
 #include "zkclient.hpp"
+
+#ifdef HOTPATH_PROF
+#if !defined(__x86_64__)
+#error "hotpath-prof reads x86-64 registers from the signal context"
+#endif
+#include <cxxabi.h>
+#include <dlfcn.h>
+#include <sys/time.h>
+#include <ucontext.h>
+
+#include <algorithm>
+#include <map>
+#endif
 
 using namespace registrar;
 
@@ -165,6 +187,172 @@ double now_s() {
 
 }  // namespace
 
+#ifdef HOTPATH_PROF
+// ---------------------------------------------------------------------------
+// sampler (see the header comment)
+
+namespace {
+constexpr int kChain = 5;  // PC + 4 return addresses
+constexpr size_t kMaxSamples = 1 << 18;
+struct ProfSample {
+  uintptr_t pc[kChain];
+};
+ProfSample* g_samples = nullptr;
+volatile size_t g_nsamples = 0;
+volatile size_t g_other_thread = 0;  // ticks that landed elsewhere
+uintptr_t g_stack_lo = 0, g_stack_hi = 0;  // the ens-io thread's stack mapping
+
+// Async-signal-safe by construction: reads registers, reads words inside
+// [g_stack_lo, g_stack_hi), writes preallocated memory. Nothing else.
+void on_sigprof(int, siginfo_t*, void* uc_) {
+  ucontext_t* uc = static_cast<ucontext_t*>(uc_);
+  uintptr_t sp = static_cast<uintptr_t>(uc->uc_mcontext.gregs[REG_RSP]);
+  if (sp < g_stack_lo || sp >= g_stack_hi) {  // not the ens-io thread
+    g_other_thread = g_other_thread + 1;
+    return;
+  }
+  size_t i = g_nsamples;
+  if (i >= kMaxSamples) return;
+  ProfSample& s = g_samples[i];
+  s.pc[0] = static_cast<uintptr_t>(uc->uc_mcontext.gregs[REG_RIP]);
+  uintptr_t fp = static_cast<uintptr_t>(uc->uc_mcontext.gregs[REG_RBP]);
+  uintptr_t floor = sp;
+  for (int d = 1; d < kChain; d++) {
+    s.pc[d] = 0;
+    // a frame record is two words, above everything already walked
+    if (fp < floor || fp + 16 > g_stack_hi || (fp & 7) != 0) {
+      fp = 0;
+      continue;
+    }
+    const uintptr_t* rec = reinterpret_cast<const uintptr_t*>(fp);
+    s.pc[d] = rec[1];
+    floor = fp + 16;
+    fp = rec[0];
+  }
+  g_nsamples = i + 1;
+}
+
+// The stack of a thread that is blocked in a system call: its stack pointer
+// from /proc/self/task/<tid>/syscall, widened to the readable mapping that
+// holds it.
+bool find_stack(long tid, uintptr_t* lo, uintptr_t* hi) {
+  char path[64], line[512];
+  snprintf(path, sizeof(path), "/proc/self/task/%ld/syscall", tid);
+  uintptr_t sp = 0;
+  for (int attempt = 0; attempt < 50 && !sp; attempt++) {
+    if (FILE* f = fopen(path, "r")) {
+      if (fgets(line, sizeof(line), f)) {
+        // "<nr> <6 args> <sp> <pc>", or "running"
+        std::vector<std::string> tok;
+        for (char* t = strtok(line, " \n"); t; t = strtok(nullptr, " \n")) tok.push_back(t);
+        if (tok.size() >= 3) sp = strtoull(tok[tok.size() - 2].c_str(), nullptr, 16);
+      }
+      fclose(f);
+    }
+    if (!sp) usleep(2000);
+  }
+  if (!sp) return false;
+  FILE* f = fopen("/proc/self/maps", "r");
+  if (!f) return false;
+  bool ok = false;
+  while (fgets(line, sizeof(line), f)) {
+    unsigned long long a = 0, b = 0;
+    char perms[8] = {0};
+    if (sscanf(line, "%llx-%llx %7s", &a, &b, perms) == 3 && sp >= a && sp < b && perms[0] == 'r') {
+      *lo = a;
+      *hi = b;
+      ok = true;
+      break;
+    }
+  }
+  fclose(f);
+  return ok;
+}
+
+bool prof_arm(long ens_tid) {
+  if (!find_stack(ens_tid, &g_stack_lo, &g_stack_hi)) {
+    fprintf(stderr, "hotpath-prof: cannot locate the ens-io thread's stack\n");
+    return false;
+  }
+  g_samples = static_cast<ProfSample*>(calloc(kMaxSamples, sizeof(ProfSample)));
+  if (!g_samples) return false;
+  struct sigaction sa;
+  memset(&sa, 0, sizeof(sa));
+  sa.sa_sigaction = on_sigprof;
+  sa.sa_flags = SA_SIGINFO | SA_RESTART;
+  sigemptyset(&sa.sa_mask);
+  sigaction(SIGPROF, &sa, nullptr);
+  struct itimerval it;
+  it.it_interval.tv_sec = 0;
+  it.it_interval.tv_usec = 1000;
+  it.it_value = it.it_interval;
+  return setitimer(ITIMER_PROF, &it, nullptr) == 0;
+}
+
+void prof_disarm() {
+  struct itimerval it;
+  memset(&it, 0, sizeof(it));
+  setitimer(ITIMER_PROF, &it, nullptr);
+  signal(SIGPROF, SIG_IGN);
+}
+
+// is_return: a return address names the instruction AFTER the call
+std::string symbol_of(uintptr_t pc, bool is_return) {
+  if (!pc) return "-";
+  Dl_info info;
+  memset(&info, 0, sizeof(info));
+  void* addr = reinterpret_cast<void*>(is_return ? pc - 1 : pc);
+  char buf[96];
+  if (dladdr(addr, &info) && info.dli_sname) {
+    int st = 0;
+    char* dem = abi::__cxa_demangle(info.dli_sname, nullptr, nullptr, &st);
+    std::string out = (st == 0 && dem) ? dem : info.dli_sname;
+    free(dem);
+    if (out.size() > 110) out = out.substr(0, 107) + "...";
+    return out;
+  }
+  if (info.dli_fname) {
+    // no dynamic symbol (a local function, an IFUNC variant): the module
+    // offset, rounded down to 256 bytes so one function's samples add up;
+    // addr2line -e <module> <offset> names it
+    const char* base = strrchr(info.dli_fname, '/');
+    snprintf(buf, sizeof(buf), "%s+0x%llx..", base ? base + 1 : info.dli_fname,
+             static_cast<unsigned long long>((pc - reinterpret_cast<uintptr_t>(info.dli_fbase)) & ~0xFFull));
+  } else {
+    snprintf(buf, sizeof(buf), "0x%llx", static_cast<unsigned long long>(pc));
+  }
+  return buf;
+}
+
+void prof_report() {
+  size_t n = g_nsamples;
+  fprintf(stderr,
+          "\nhotpath-prof: %zu samples on ens-io, %zu ticks on other threads (ITIMER_PROF asked for 1 ms; the kernel "
+          "delivers at its own tick rate)\n",
+          n, static_cast<size_t>(g_other_thread));
+  if (!n) return;
+  std::map<std::string, size_t> self, chains;
+  for (size_t i = 0; i < n; i++) {
+    const ProfSample& s = g_samples[i];
+    self[symbol_of(s.pc[0], false)]++;
+    std::string c = symbol_of(s.pc[0], false);
+    for (int d = 1; d < 4; d++) c += " <- " + symbol_of(s.pc[d], true);
+    chains[c]++;
+  }
+  auto top = [&](const std::map<std::string, size_t>& m, size_t k, const char* title) {
+    std::vector<std::pair<size_t, std::string>> v;
+    for (auto& kv : m) v.push_back({kv.second, kv.first});
+    std::sort(v.begin(), v.end(), [](auto& a, auto& b) { return a.first > b.first; });
+    fprintf(stderr, "--- %s ---\n", title);
+    for (size_t i = 0; i < v.size() && i < k; i++)
+      fprintf(stderr, "%6.2f%% %6zu  %s\n", 100.0 * v[i].first / n, v[i].first, v[i].second.c_str());
+  };
+  top(self, 40, "self time per symbol");
+  top(chains, 25, "most common 4-deep chains (leaf <- callers)");
+}
+}  // namespace
+#endif  // HOTPATH_PROF
+
 int main(int argc, char** argv) {
   signal(SIGPIPE, SIG_IGN);
   int n = argc > 1 ? atoi(argv[1]) : 1000;
@@ -243,6 +431,10 @@ int main(int argc, char** argv) {
   for (int i = 0; i < warmup; i++)
     if (!step(nullptr)) return 1;
 
+#ifdef HOTPATH_PROF
+  if (!prof_arm(ens_tid)) return 1;
+#endif
+
   const long tids[3] = {ens_tid, cli_tid, caller_tid};
   const char* names[3] = {"ens-io", "zk-loop", "caller"};
   Sample s0[3], s1[3];
@@ -258,6 +450,9 @@ int main(int argc, char** argv) {
   }
   double wall = now_s() - t0;
   for (int t = 0; t < 3; t++) s1[t] = sample(tids[t]);
+#ifdef HOTPATH_PROF
+  prof_disarm();
+#endif
 
   // delete-only batches (the unregister path), re-registering in between;
   // only the delete batch is counted
@@ -302,5 +497,8 @@ int main(int argc, char** argv) {
   printf(", \"requests\": {\"create\": %llu, \"delete\": %llu, \"exists\": %llu}}\n",
          static_cast<unsigned long long>(counters["create"]), static_cast<unsigned long long>(counters["delete"]),
          static_cast<unsigned long long>(counters["exists"]));
+#ifdef HOTPATH_PROF
+  prof_report();
+#endif
   return 0;
 }

@@ -24,7 +24,9 @@
 #include <new>
 #include <queue>
 #include <stdexcept>
+#include <string_view>
 #include <thread>
+#include <utility>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
@@ -86,6 +88,69 @@ class RecvBuf {
  private:
   char* data_ = nullptr;
   size_t cap_ = 0, begin_ = 0, end_ = 0;
+};
+
+// Output byte buffer in the style of RecvBuf: reserve() hands out
+// uninitialised room at the tail (a reply of known size bound is encoded
+// straight into it), commit() publishes what was written. append/erase_front/
+// swap cover what the send path did with std::string before.
+class ByteBuf {
+ public:
+  ByteBuf() = default;
+  ~ByteBuf() { free(data_); }
+  ByteBuf(const ByteBuf&) = delete;
+  ByteBuf& operator=(const ByteBuf&) = delete;
+
+  size_t size() const { return size_; }
+  bool empty() const { return size_ == 0; }
+  const char* data() const { return data_; }
+  char* data() { return data_; }
+  void clear() { size_ = 0; }
+
+  // at least n writable bytes behind size(); valid until the next reserve()
+  char* reserve(size_t n) {
+    if (cap_ - size_ < n) grow(n);
+    return data_ + size_;
+  }
+  void commit(size_t n) { size_ += n; }
+
+  void append(const char* p, size_t n) {
+    if (n == 0) return;
+    memcpy(reserve(n), p, n);
+    size_ += n;
+  }
+  void append(std::string_view s) { append(s.data(), s.size()); }
+  // bytes [pos, pos + n) of another buffer
+  void append(const ByteBuf& o, size_t pos, size_t n) { append(o.data_ + pos, n); }
+
+  void erase_front(size_t n) {
+    if (n >= size_) {
+      size_ = 0;
+      return;
+    }
+    if (n == 0) return;
+    memmove(data_, data_ + n, size_ - n);
+    size_ -= n;
+  }
+
+  void swap(ByteBuf& o) {
+    std::swap(data_, o.data_);
+    std::swap(cap_, o.cap_);
+    std::swap(size_, o.size_);
+  }
+
+ private:
+  void grow(size_t n) {
+    size_t ncap = cap_ * 2 > size_ + n ? cap_ * 2 : size_ + n;
+    if (ncap < 256) ncap = 256;
+    char* nd = static_cast<char*>(realloc(data_, ncap));
+    if (!nd) throw std::bad_alloc();
+    data_ = nd;
+    cap_ = ncap;
+  }
+
+  char* data_ = nullptr;
+  size_t cap_ = 0, size_ = 0;
 };
 
 class EventLoop {

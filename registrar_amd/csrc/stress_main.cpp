@@ -140,6 +140,10 @@ int main(int argc, char** argv) {
           mops.push_back(cr);
           client.multi(mops, nullptr);  // rc may be conn-loss under chaos
         }
+        // setData past the node block's inline capacity and back (the node
+        // stays put; its data moves out of line and in again)
+        client.set(res.znodes[0], std::string(6000, 'g'), -1, nullptr);
+        client.set(res.znodes[0], "small", -1, nullptr);
         zk::RetryPolicy rp;
         rp.max_attempts = 1;
         rp.initial_delay_ms = 10;
