@@ -179,6 +179,7 @@ PYBIND11_MODULE(_core, m) {
       .def("session_ids", &zk::Ensemble::session_ids)
       .def("zxid", &zk::Ensemble::zxid)
       .def("counters", &zk::Ensemble::counters)
+      .def("audit", &zk::Ensemble::audit, py::call_guard<py::gil_scoped_release>())
       .def_static("node_store_layout", [] {
         zk::NodeStoreLayout l = zk::Ensemble::node_store_layout();
         py::dict d;

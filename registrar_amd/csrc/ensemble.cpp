@@ -1696,6 +1696,13 @@ struct Ensemble::Impl {
     // Drain one node at a time: pop it under eph_mu (a linked node cannot be
     // freed — whoever removes it must take eph_mu to unlink it first), copy
     // its path, then delete by path with no lock held, as before.
+    // INVARIANT: between the pop and the delete no lock is held, and
+    // delete_node looks the PATH up again. The node it finds may no longer be
+    // the one popped: another session can have deleted the stale node and
+    // created its own at the same path in that window (the registrar's
+    // takeover of a dead predecessor's paths does exactly this). So the
+    // delete is conditional on the node still being owned by the dying
+    // session; anything else at that path is somebody else's and stays.
     std::string p;
     while (true) {
       {
@@ -1705,7 +1712,7 @@ struct Ensemble::Impl {
         p.assign(n->path());
         eph_unlink(*s, *n);
       }
-      delete_node(p);
+      delete_node(p, nullptr, s.get());
     }
     // stale watch registrations for this session are skipped at fire time
     uint64_t cid = s->conn_id.load();
@@ -1734,6 +1741,173 @@ struct Ensemble::Impl {
       }
       schedule_sweep();
     });
+  }
+
+  // ---------------- structural audit (tests, stress driver) ----------------
+
+  // Every structural invariant of the tree, checked against the stored
+  // state; one line per violation, none when the tree is sound. Never on a
+  // request path. Locks: all shards in index order, then session_mu for a
+  // snapshot, then every snapshotted session's eph_mu (shard → eph_mu, as the
+  // handlers). kill_session moves a session's list and `alive` under eph_mu
+  // alone, so while an expiry is in flight the list-against-node checks can
+  // name a node that has been popped and not yet deleted: callers audit only
+  // when no expiry is running. Marked cold so that its bulk stays out of the
+  // handlers' text.
+  __attribute__((cold, noinline)) std::vector<std::string> audit() {
+    std::vector<std::string> out;
+    auto bad = [&out](std::string_view where, const std::string& what) {
+      out.push_back(std::string(where) + ": " + what);
+    };
+    std::vector<std::unique_lock<std::mutex>> locks;
+    locks.reserve(kShards);
+    for (auto& sh : shards) locks.emplace_back(sh.mu);
+    std::vector<SessionPtr> snap;
+    {
+      std::lock_guard<std::mutex> g(session_mu);
+      for (const auto& kv : sessions) {
+        if (kv.first != kv.second->id) bad("session " + std::to_string(kv.first), "keyed under another id");
+        snap.push_back(kv.second);
+      }
+    }
+    std::sort(snap.begin(), snap.end(), [](const SessionPtr& a, const SessionPtr& b) { return a->id < b->id; });
+    std::vector<std::unique_lock<std::mutex>> eph_locks;
+    eph_locks.reserve(snap.size());
+    std::unordered_set<const Session*> known;
+    for (const auto& s : snap) {
+      eph_locks.emplace_back(s->eph_mu);
+      known.insert(s.get());
+    }
+
+    size_t total = 0;
+    for (auto& sh : shards) total += sh.nodes.count;
+
+    for (size_t si = 0; si < kShards; si++) {
+      NodeStore& st = shards[si].nodes;
+      std::string shard_name = "shard " + std::to_string(si);
+      size_t seen = 0;
+      for (size_t b = 0; b < st.nbuckets; b++) {
+        for (ZNode* n = st.buckets[b]; n && seen <= st.count; n = n->chain) {
+          seen++;
+          std::string_view path = n->path();
+          if (!valid_path(path)) {
+            bad(shard_name, "node with an invalid path in bucket " + std::to_string(b));
+            continue;
+          }
+          if (n->hash != std::hash<std::string_view>{}(path)) bad(path, "stored hash is not the hash of the path");
+          if (n->hash % kShards != si) bad(path, "sits in shard " + std::to_string(si) + ", not the one its hash selects");
+          if (st.bucket_of(n->hash) != b) bad(path, "sits in bucket " + std::to_string(b) + ", not the one its hash selects");
+
+          // parent link
+          if (path == "/") {
+            if (n->parent) bad(path, "root has a parent");
+          } else if (!n->parent) {
+            bad(path, "no parent link");
+          } else if (find_node(ref_of(parent_view(path))) != n->parent) {
+            bad(path, "parent link is not the node at the parent path");
+          }
+
+          // children: the sibling list, its links, both counts
+          int32_t walked = 0;
+          const ZNode* prev = nullptr;
+          for (const ZNode* c = n->first_child; c; c = c->sib_next) {
+            if (static_cast<size_t>(walked) > total) {
+              bad(path, "sibling list does not end");
+              break;
+            }
+            walked++;
+            if (c->parent != n) bad(path, "child " + std::string(c->path()) + " points at another parent");
+            if (c->sib_prev != prev) bad(path, "child " + std::string(c->path()) + " has a wrong sib_prev");
+            prev = c;
+          }
+          if (walked != n->nchildren)
+            bad(path, "sibling list has " + std::to_string(walked) + " nodes, nchildren is " +
+                          std::to_string(n->nchildren));
+          if (n->stat.num_children != n->nchildren)
+            bad(path, "stat.num_children " + std::to_string(n->stat.num_children) + " != nchildren " +
+                          std::to_string(n->nchildren));
+
+          // data placement
+          if (n->stat.data_length != static_cast<int32_t>(n->data_len))
+            bad(path, "stat.data_length " + std::to_string(n->stat.data_length) + " != data_len " +
+                          std::to_string(n->data_len));
+          if (n->path_len > n->inline_cap) {
+            bad(path, "path longer than the block");
+          } else {
+            bool fits = n->data_len <= n->inline_cap - n->path_len;
+            if (fits && n->ext) bad(path, "data fits the block but is out of line");
+            if (!fits && !n->ext) bad(path, "data does not fit the block but there is no out-of-line buffer");
+            if (n->ext && n->ext_cap < n->data_len) bad(path, "out-of-line buffer smaller than the data");
+          }
+
+          // ownership
+          Session* owner = n->owner.get();
+          bool linked = false;
+          if (owner) {
+            if (known.count(owner)) {
+              linked = n->eph_linked;  // its eph_mu is held
+            } else {
+              std::lock_guard<std::mutex> eg(owner->eph_mu);
+              linked = n->eph_linked;
+            }
+          }
+          if ((n->stat.ephemeral_owner != 0) != (owner != nullptr && linked))
+            bad(path, "stat.ephemeral_owner " + std::to_string(n->stat.ephemeral_owner) + " but owner " +
+                          (owner ? "set" : "unset") + ", " + (linked ? "linked" : "not linked"));
+          if (owner) {
+            if (!known.count(owner)) bad(path, "owner session " + std::to_string(owner->id) + " is not in sessions");
+            if (!owner->alive.load(std::memory_order_acquire))
+              bad(path, "owner session " + std::to_string(owner->id) + " is not alive");
+            if (owner->id != n->stat.ephemeral_owner)
+              bad(path, "owner session " + std::to_string(owner->id) + " != stat.ephemeral_owner " +
+                            std::to_string(n->stat.ephemeral_owner));
+          }
+        }
+      }
+      if (seen != st.count)
+        bad(shard_name, "chains hold " + std::to_string(seen) + " nodes, count is " + std::to_string(st.count));
+
+      // free lists
+      size_t sum = 0;
+      for (size_t c = 0; c < kNumClasses; c++) {
+        sum += st.free_count[c];
+        if (st.free_count[c] > kMaxCachedPerClass)
+          bad(shard_name, "class " + std::to_string(c) + " caches " + std::to_string(st.free_count[c]) + " blocks");
+        size_t len = 0;
+        for (NodeStore::FreeBlock* f = st.free_head[c]; f && len <= st.free_count[c]; f = f->next) len++;
+        if (len != st.free_count[c])
+          bad(shard_name, "class " + std::to_string(c) + " free list length differs from free_count " +
+                              std::to_string(st.free_count[c]));
+      }
+      if (sum != st.cached)
+        bad(shard_name, "cached " + std::to_string(st.cached) + " != sum of free_count " + std::to_string(sum));
+    }
+
+    // each session's ephemeral list against the table
+    for (const auto& s : snap) {
+      std::string name = "session " + std::to_string(s->id);
+      size_t len = 0;
+      const ZNode* prev = nullptr;
+      for (ZNode* n = s->eph_head; n; n = n->eph_next) {
+        if (len > total) {
+          bad(name, "ephemeral list does not end");
+          break;
+        }
+        len++;
+        if (n->eph_prev != prev) bad(name, "ephemeral list has a wrong eph_prev");
+        prev = n;
+        if (find_node(n->ref()) != n) {
+          bad(name, "listed node is not in the table at its path");
+          continue;
+        }
+        if (n->owner.get() != s.get()) bad(name, "lists " + std::string(n->path()) + ", which has another owner");
+        if (!n->eph_linked) bad(name, "lists " + std::string(n->path()) + ", which is not marked linked");
+      }
+      if (len != s->eph_count)
+        bad(name, "ephemeral list has " + std::to_string(len) + " nodes, eph_count is " +
+                      std::to_string(s->eph_count));
+    }
+    return out;
   }
 
   // ---------------- watches (shard lock held) ----------------
@@ -2336,6 +2510,8 @@ std::map<std::string, uint64_t> Ensemble::counters() const {
   out["node_blocks_cached"] = cached;
   return out;
 }
+
+std::vector<std::string> Ensemble::audit() const { return impl_->audit(); }
 
 NodeStoreLayout Ensemble::node_store_layout() {
   NodeStoreLayout l;

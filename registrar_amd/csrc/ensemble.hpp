@@ -108,6 +108,12 @@ class Ensemble {
   // node blocks the shards currently hold for reuse (always present)
   std::map<std::string, uint64_t> counters() const;
   static NodeStoreLayout node_store_layout();
+  // Structural audit of the whole tree (parent/sibling links, counts, data
+  // placement, hashes and buckets, ephemeral ownership against the sessions,
+  // free lists): one human-readable line per violation, empty when sound.
+  // Takes every shard lock; for tests and the stress driver, never for a
+  // request path. Call it only while no session expiry is in flight.
+  std::vector<std::string> audit() const;
 
  private:
   struct Impl;

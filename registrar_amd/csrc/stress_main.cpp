@@ -7,8 +7,16 @@
 //   - an in-process 3-server ensemble,
 //   - N concurrent registrar clients doing register → heartbeat → unregister
 //     cycles with watches armed,
-//   - a chaos thread expiring random sessions and kill/restarting servers.
-// Exit code 0 = every cycle behaved; sanitizers report races/leaks.
+//   - a chaos thread expiring random sessions and kill/restarting servers,
+//   - then a contested phase: PAIRS of clients register the same domain, host
+//     and aliases, so each cleans up and recreates the other's znodes (one of
+//     a pair by atomic swap, one by cleanup + create) while the chaos thread
+//     goes on expiring sessions. A register or heartbeat that loses to its
+//     peer there is expected and not counted.
+// At the end, with every client closed and every session gone, the tree must
+// pass Ensemble::audit() and hold no ephemeral.
+// Exit code 0 = every cycle behaved and the end state is sound; sanitizers
+// report races/leaks.
 #include <dirent.h>
 #include <execinfo.h>
 #include <signal.h>
@@ -70,11 +78,14 @@ int main(int argc, char** argv) {
   signal(SIGPIPE, SIG_IGN);  // belt: library writes already use MSG_NOSIGNAL
   int nclients = 4;
   int seconds = 8;
+  int contested_seconds = -1;  // default: half of -t
   if (const char* wd = getenv("STRESS_WATCHDOG")) arm_watchdog(atoi(wd));
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "-c") && i + 1 < argc) nclients = atoi(argv[++i]);
     if (!strcmp(argv[i], "-t") && i + 1 < argc) seconds = atoi(argv[++i]);
+    if (!strcmp(argv[i], "-p") && i + 1 < argc) contested_seconds = atoi(argv[++i]);
   }
+  if (contested_seconds < 0) contested_seconds = seconds / 2;
 
   Logger log("stress");
   log.set_level(LogLevel::Error);
@@ -93,8 +104,12 @@ int main(int argc, char** argv) {
   std::atomic<bool> stop{false};
   std::atomic<uint64_t> cycles{0};
   std::atomic<uint64_t> failures{0};
+  std::atomic<uint64_t> contested_cycles{0};
 
-  auto client_fn = [&](int idx) {
+  // contested: clients 2k and 2k+1 share one registration (see the header)
+  auto client_fn = [&](int idx, bool contested) {
+    int who = contested ? idx / 2 : idx;
+    std::string tag = std::string(contested ? "p" : "c") + std::to_string(who);
     while (!stop.load()) {
       zk::ZkClientConfig ccfg;
       for (auto& s : servers) ccfg.servers.push_back({s.first, s.second});
@@ -108,17 +123,18 @@ int main(int argc, char** argv) {
       if (!client.wait_connected(5000)) continue;
 
       RegistrationConfig reg;
-      reg.domain = "c" + std::to_string(idx) + ".stress.test";
+      reg.domain = tag + ".stress.test";
       reg.type = "host";
       reg.admin_ip = "127.0.0.1";
-      reg.hostname = "h" + std::to_string(idx);
+      reg.hostname = "h" + std::to_string(who);
       reg.settle_ms = 0;
-      for (int a = 0; a < 20; a++) reg.aliases.push_back("a" + std::to_string(a) + ".c" + std::to_string(idx) + ".stress.test");
+      reg.atomic_swap = contested && idx % 2 == 0;
+      for (int a = 0; a < 20; a++) reg.aliases.push_back("a" + std::to_string(a) + "." + tag + ".stress.test");
 
       while (!stop.load() && client.state() == zk::SessionState::Connected) {
         RegisterResult res = register_node(client, reg, log);
         if (res.rc != zk::kZOk) {
-          failures.fetch_add(1);
+          if (!contested) failures.fetch_add(1);
           break;
         }
         // arm some watches like a Binder reader would
@@ -148,9 +164,11 @@ int main(int argc, char** argv) {
         rp.max_attempts = 1;
         rp.initial_delay_ms = 10;
         int rc = client.heartbeat(res.znodes, rp, nullptr);
-        if (rc != zk::kZOk && rc != zk::kZConnectionLoss && rc != zk::kZSessionExpired) failures.fetch_add(1);
+        // contested: the peer may have replaced or removed any of the nodes
+        if (!contested && rc != zk::kZOk && rc != zk::kZConnectionLoss && rc != zk::kZSessionExpired)
+          failures.fetch_add(1);
         unregister_node(client, res.znodes, log);
-        cycles.fetch_add(1);
+        (contested ? contested_cycles : cycles).fetch_add(1);
       }
       client.close();
     }
@@ -197,19 +215,61 @@ int main(int argc, char** argv) {
       if (!ens.server_up(i)) ens.restart_server(i);
   };
 
-  std::vector<std::thread> threads;
-  for (int i = 0; i < nclients; i++) threads.emplace_back(client_fn, i);
-  std::thread chaos(chaos_fn);
+  for (int phase = 0; phase < 2; phase++) {
+    bool contested = phase == 1;
+    int secs = contested ? contested_seconds : seconds;
+    if (secs <= 0) continue;
+    stop.store(false);
+    std::vector<std::thread> threads;
+    for (int i = 0; i < nclients; i++) threads.emplace_back(client_fn, i, contested);
+    std::thread chaos(chaos_fn);
+    std::this_thread::sleep_for(std::chrono::seconds(secs));
+    stop.store(true);
+    for (auto& t : threads) t.join();
+    chaos.join();
+  }
 
-  std::this_thread::sleep_for(std::chrono::seconds(seconds));
-  stop.store(true);
-  for (auto& t : threads) t.join();
-  chaos.join();
+  // End state. Every client is closed, so every session ends: by its close,
+  // or (where the close was lost to a killed server) by the expiry sweep. A
+  // close is acknowledged before the ensemble has drained the session's
+  // ephemerals, and the audit is only meaningful with no drain in flight, so
+  // wait for the sessions to go and give the last drain a moment to finish.
+  // A real violation does not go away by waiting.
+  auto deadline = std::chrono::steady_clock::now() + std::chrono::seconds(15);
+  while (!ens.session_ids().empty() && std::chrono::steady_clock::now() < deadline)
+    std::this_thread::sleep_for(std::chrono::milliseconds(20));
+  size_t sessions_left = ens.session_ids().size();
+  std::vector<std::string> violations = ens.audit();
+  deadline = std::chrono::steady_clock::now() + std::chrono::seconds(2);
+  while (!violations.empty() && std::chrono::steady_clock::now() < deadline) {
+    std::this_thread::sleep_for(std::chrono::milliseconds(20));
+    violations = ens.audit();
+  }
+  size_t ephemerals_left = ens.ephemeral_count();
   ens.stop();
 
-  printf("stress: %llu cycles, %llu hard failures\n", static_cast<unsigned long long>(cycles.load()),
-         static_cast<unsigned long long>(failures.load()));
+  printf("stress: %llu cycles, %llu hard failures, %llu contested cycles\n",
+         static_cast<unsigned long long>(cycles.load()), static_cast<unsigned long long>(failures.load()),
+         static_cast<unsigned long long>(contested_cycles.load()));
+  bool sound = true;
+  if (sessions_left != 0) {
+    printf("stress: %zu sessions still alive after every client closed\n", sessions_left);
+    sound = false;
+  }
+  if (ephemerals_left != 0) {
+    printf("stress: %zu ephemerals left\n", ephemerals_left);
+    sound = false;
+  }
+  for (const auto& v : violations) {
+    printf("stress: audit: %s\n", v.c_str());
+    sound = false;
+  }
+  if (contested_seconds > 0 && contested_cycles.load() == 0) {
+    printf("stress: the contested phase completed no cycle\n");
+    sound = false;
+  }
   // hard failures are register errors while connected — tolerate a few from
   // chaos timing, fail on systematic breakage
-  return (cycles.load() > 0 && failures.load() < cycles.load() / 4 + 16) ? 0 : 1;
+  bool behaved = cycles.load() > 0 && failures.load() < cycles.load() / 4 + 16;
+  return (behaved && sound) ? 0 : 1;
 }

@@ -284,6 +284,7 @@ def test_set_data_across_inline_capacity(ensemble):
         assert a.delete_many(kids) == [ra.ZOK] * 10
         assert a.delete_("/s") == ra.ZOK
         assert ensemble.node_count() == 0
+        assert ensemble.audit() == []
     finally:
         a.close()
         b.close()
@@ -401,6 +402,7 @@ def test_two_io_threads_recycle_and_kill():
         assert ens.node_count() == 3 + 150
         for p in ("/p0", "/p1", "/shared"):
             assert ens.get(p)["stat"]["numChildren"] == 50
+        assert ens.audit() == []  # the expiry is over: the victim's id is gone and so are its nodes
     finally:
         for c in clients:
             c.close()
