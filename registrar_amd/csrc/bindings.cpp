@@ -406,7 +406,7 @@ PYBIND11_MODULE(_core, m) {
                py::gil_scoped_release rel;
                res = register_prepared(c, prep, log);
              }
-             return py::make_tuple(res.rc, res.error, res.znodes);
+             return py::make_tuple(res.rc, res.error, res.znodes());
            },
            py::arg("client"), py::arg("log_level") = "warn")
       .def("heartbeat",
@@ -431,7 +431,7 @@ PYBIND11_MODULE(_core, m) {
             py::gil_scoped_release rel;
             res = register_node(c, cfg, log);
           }
-          return py::make_tuple(res.rc, res.error, res.znodes);
+          return py::make_tuple(res.rc, res.error, res.znodes());
         },
         py::arg("client"), py::arg("registration_json"), py::arg("log_level") = "warn");
   m.def("unregister_node",

@@ -15,9 +15,12 @@
 //   - per-connection output buffers have their own mutex; replies queue per
 //     event drain and flush as a few large writes.
 //
-// Global lock order: shard(s) → session_mu → conns_mu → conn->out_mu.
-// kill_session drains the ephemeral set with no other lock held before
-// taking shard locks (see the phase comments).
+// Global lock order: shard(s) by ascending index → one session's eph_mu →
+// session_mu → conns_mu → conn->out_mu. A thread blocks on a mutex only while
+// everything it holds comes earlier in that order; a drain that carries its
+// parent shard and eph_mu across sibling requests takes child shards with
+// try_lock (struct Carry). kill_session drains the ephemeral set with no
+// other lock held before taking shard locks (see the phase comments).
 #include "ensemble.hpp"
 
 #include <arpa/inet.h>
@@ -45,6 +48,14 @@ void set_nonblock(int fd) {
 void set_nodelay(int fd) {
   int one = 1;
   setsockopt(fd, IPPROTO_TCP, TCP_NODELAY, &one, sizeof(one));
+}
+
+inline void spin_pause() {
+#if defined(__x86_64__) || defined(__i386__)
+  __builtin_ia32_pause();
+#else
+  std::this_thread::yield();
+#endif
 }
 
 int64_t wall_ms() {
@@ -100,6 +111,7 @@ struct Ensemble::Impl {
   static constexpr size_t kShards = 64;
 
   struct ZNode;
+  struct Carry;
 
   struct Session {
     int64_t id = 0;
@@ -139,7 +151,23 @@ struct Ensemble::Impl {
     ZNode* first_child = nullptr;
     ZNode* sib_prev = nullptr;
     ZNode* sib_next = nullptr;
-    SessionPtr owner;  // ephemeral owner (null for persistent nodes)
+    // Ephemeral owner (null for persistent nodes). A plain pointer: the node
+    // never keeps its session alive, the session outlives the node instead.
+    //   - handle_create sets it only after reading alive==true under eph_mu,
+    //     and links the node in that same section; a create that sees !alive
+    //     links nothing and sets nothing.
+    //   - kill_session holds the SessionPtr on its stack until its drain has
+    //     removed every node linked to the session: a linked node is in the
+    //     drain's list, and a node the drain has popped is deleted (by the
+    //     drain, or by another request that takes the node's shard lock
+    //     first) before the drain moves on, since both need that shard lock.
+    //   - handle_multi may set it on an unlinked node when the session died
+    //     mid-transaction; it keeps the SessionPtr on its stack until the
+    //     rollback has removed that node (same shard-lock argument).
+    //   - until kill_session runs, `sessions` holds the session.
+    // It is dereferenced only with the node's shard locked, i.e. while the
+    // node is in the table. Teardown (~NodeStore, release) never reads it.
+    Session* owner = nullptr;
     ZNode* eph_prev = nullptr;
     ZNode* eph_next = nullptr;
     char* ext = nullptr;     // out-of-line data, null while the data is inline
@@ -334,7 +362,7 @@ struct Ensemble::Impl {
       if (n->parent || n->eph_linked || n->first_child) std::abort();  // invariant
       if (n->ext) ::operator delete(n->ext);
       uint8_t cls = n->size_class;
-      n->~ZNode();  // drops the owner reference
+      n->~ZNode();
       if (cls != kNoClass && free_count[cls] < kMaxCachedPerClass) {
         FreeBlock* f = reinterpret_cast<FreeBlock*>(n);
         f->next = free_head[cls];
@@ -349,6 +377,9 @@ struct Ensemble::Impl {
 
   struct Shard {
     std::mutex mu;
+    // threads waiting in lock_shard; a drain that carries mu reads it before
+    // every request (acquire_for)
+    std::atomic<uint32_t> waiters{0};
     NodeStore nodes;
     WatchMap data_watches;
     WatchMap child_watches;
@@ -371,6 +402,7 @@ struct Ensemble::Impl {
     int64_t drain_mono_ms = 0;
     int64_t drain_wall_ms = 0;
     PathRef last_parent{std::string_view(), 0};
+    Carry* carry = nullptr;  // the running drain's carried locks (process_frames)
     std::string scratch;  // variable-size replies are built here, then staged
     // replies produced during a drain are staged here without a lock and
     // move to outbuf once, at the flush that ends the drain
@@ -398,16 +430,76 @@ struct Ensemble::Impl {
     bool up = false;
   };
 
-  // One counter block per IO loop (slot = io_idx % kCounterSlots), each on
-  // cache lines of its own, so IO threads do not bounce a shared line on
-  // every request; counters() sums the slots. Increments stay atomic RMWs so
-  // loops that share a slot (more than kCounterSlots IO threads) still count
-  // exactly.
+  // One counter block per IO loop, each on cache lines of its own, allocated
+  // by start() once the pool's size is known. A block has exactly one writer,
+  // its loop's thread, so an increment is a relaxed load and a relaxed store
+  // (bump below), not an atomic read-modify-write; counters() sums the blocks
+  // with relaxed loads from any thread and stays exact.
+  // tree_locks: shard and eph_mu acquisitions made by request handlers.
   struct alignas(128) OpCounters {
     std::atomic<uint64_t> connect{0}, create{0}, del{0}, exists{0}, get_data{0}, set_data{0},
-        get_children{0}, ping{0}, close_session{0}, unknown{0};
+        get_children{0}, ping{0}, close_session{0}, unknown{0}, tree_locks{0};
   };
-  static constexpr size_t kCounterSlots = 16;
+  static void bump(std::atomic<uint64_t>& a, uint64_t by = 1) {
+    a.store(a.load(std::memory_order_relaxed) + by, std::memory_order_relaxed);
+  }
+
+  // Most create/delete requests one drain serves under the same carried
+  // locks before it lets them go and takes them afresh (see Carry). It bounds
+  // how long another connection waits for a shard or for a session's eph_mu.
+  static constexpr uint32_t kCarryBound = 32;
+
+  // The locks a drain carries from one create / create2 / delete frame to the
+  // next, so a run of siblings locks its parent's shard and its own session's
+  // eph_mu once per run, not once per request.
+  //
+  // Canonical lock order: shards by ascending index, then ONE eph_mu (two are
+  // never held at once), then session_mu → conns_mu → conn->out_mu.
+  // Blocking rule: a thread may BLOCK on a mutex only if everything it holds
+  // comes earlier in that order. A carrying thread holds the parent's shard
+  // and possibly eph_mu, so it takes a child shard with try_lock only; if
+  // that fails it releases everything it carries and takes the locks in
+  // canonical order (acquire_for below). Taking eph_mu while holding shards,
+  // and the watch path's session_mu/conns_mu/out_mu while holding all of
+  // them, blocks in order.
+  //
+  // A carry also ends at a parent in another shard, after kCarryBound
+  // requests, and as soon as another thread is seen waiting for the carried
+  // shard (Shard::waiters, lock_shard): with several connections at work a
+  // shard changes hands within about one request.
+  //
+  // process_frames owns the one Carry of a drain; its destructor releases, so
+  // no way out of the drain leaves a mutex locked. Everything that is not a
+  // plain create/create2/delete releases first (handle_frame): any other op
+  // may lock the carried shard itself (an exists on the parent's own shard
+  // would otherwise deadlock on a std::mutex this thread holds), and
+  // closeSession runs kill_session, which wants eph_mu with nothing held.
+  struct Carry {
+    std::mutex* shard_mu = nullptr;  // the parent shard's mutex, locked
+    size_t shard_idx = 0;
+    Session* eph = nullptr;  // the session whose eph_mu is held
+    uint32_t served = 0;     // requests served since shard_mu was taken
+
+    Carry() = default;
+    Carry(const Carry&) = delete;
+    Carry& operator=(const Carry&) = delete;
+    ~Carry() { release(); }
+
+    void drop_eph() {
+      if (eph) {
+        eph->eph_mu.unlock();
+        eph = nullptr;
+      }
+    }
+    void release() {
+      drop_eph();
+      if (shard_mu) {
+        shard_mu->unlock();
+        shard_mu = nullptr;
+      }
+      served = 0;
+    }
+  };
 
   EnsembleConfig cfg;
   Logger log;
@@ -417,8 +509,9 @@ struct Ensemble::Impl {
   std::atomic<bool> started{false};
   std::atomic<int> latency_ms{0};
   std::atomic<int64_t> zxid_counter{0};
-  std::array<OpCounters, kCounterSlots> ops;
-  OpCounters& cnt(const Conn* c) { return ops[c->io_idx % kCounterSlots]; }
+  std::unique_ptr<OpCounters[]> ops;  // loops.size() blocks, made by the first start()
+  size_t n_ops = 0;
+  OpCounters& cnt(const Conn* c) { return ops[c->io_idx]; }
 
   std::array<Shard, kShards> shards;
 
@@ -527,20 +620,29 @@ struct Ensemble::Impl {
   // index. Runs inside the node's shard lock, BEFORE the erase: the index
   // holds node pointers, so a node must never be freed (or, worse, recycled)
   // while linked.
-  static void detach_ephemeral(ZNode& n) {
-    if (!n.owner) return;
+  // `held`: the session whose eph_mu the caller holds already (a drain's
+  // carry), or null. Returns the number of mutexes it took.
+  static int detach_ephemeral(ZNode& n, Session* held = nullptr) {
+    if (!n.owner) return 0;
+    if (n.owner == held) {
+      eph_unlink(*n.owner, n);
+      return 0;
+    }
     std::lock_guard<std::mutex> eg(n.owner->eph_mu);
     eph_unlink(*n.owner, n);
+    return 1;
   }
 
   // Remove node n (no children; its shard csh and its parent's shard psh
   // both locked): session index, parent link + parent Stat, watches
   // (parent's child watch first, then NodeDeleted), erase. Returns the zxid
   // the removal committed at.
-  int64_t remove_node_locked(Shard& csh, ZNode* np, Shard& psh) {
+  int64_t remove_node_locked(Shard& csh, ZNode* np, Shard& psh, Session* eph_held = nullptr,
+                             int* locks_taken = nullptr) {
     ZNode& n = *np;
     int64_t z = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
-    detach_ephemeral(n);
+    int took = detach_ephemeral(n, eph_held);
+    if (locks_taken) *locks_taken += took;
     if (ZNode* par = n.parent) {
       unlink_child(n);
       par->stat.cversion++;
@@ -560,6 +662,74 @@ struct Ensemble::Impl {
     return c->last_parent;
   }
 
+  // The shard locks of one create/delete under the carry k. The parent's
+  // shard (index pidx) ends up held in k: found there from the previous
+  // request, or taken now. The child's shard (cidx) is returned as a lock of
+  // the caller's scope, empty when the child lives in the parent's shard.
+  // While k holds anything the child is only tried; see Carry for the rule.
+  std::unique_lock<std::mutex> acquire_for(Carry& k, size_t cidx, size_t pidx, int* locks) {
+    // the carry ends at its bound, at a parent in another shard, and as soon
+    // as anybody is seen waiting for the carried shard (lock_shard)
+    if (k.shard_mu && (k.shard_idx != pidx || k.served >= kCarryBound ||
+                       shards[k.shard_idx].waiters.load(std::memory_order_relaxed) != 0))
+      k.release();
+    std::unique_lock<std::mutex> child;
+    if (k.shard_mu && cidx != pidx) {
+      child = std::unique_lock<std::mutex>(shards[cidx].mu, std::try_to_lock);
+      if (child.owns_lock())
+        ++*locks;
+      else
+        k.release();  // contended: let go of everything, then queue in order
+    }
+    if (!k.shard_mu) {
+      // nothing is held here (release drops eph_mu too): ascending, blocking
+      if (cidx < pidx) {
+        child = lock_shard(shards[cidx]);
+        ++*locks;
+      }
+      lock_shard(shards[pidx]).release();  // the carry owns it from here
+      k.shard_mu = &shards[pidx].mu;
+      k.shard_idx = pidx;
+      ++*locks;
+      if (cidx > pidx) {
+        child = lock_shard(shards[cidx]);
+        ++*locks;
+      }
+    }
+    k.served++;
+    return child;
+  }
+
+  // A blocking shard acquisition by a request handler (the caller holds
+  // nothing later in the lock order). Uncontended it is one try_lock. When
+  // the shard is taken, the holder may be a drain carrying it across many
+  // requests, so the wait is announced in sh.waiters: a carrying thread looks
+  // at that count before each request and lets go at once. That takes it
+  // about one request, so spinning for a moment first is cheaper than going
+  // to sleep in the kernel and being woken.
+  static std::unique_lock<std::mutex> lock_shard(Shard& sh) {
+    std::unique_lock<std::mutex> lk(sh.mu, std::try_to_lock);
+    if (lk.owns_lock()) return lk;
+    sh.waiters.fetch_add(1, std::memory_order_relaxed);
+    for (int i = 0; i < 512 && !lk.owns_lock(); i++) {
+      spin_pause();
+      lk.try_lock();
+    }
+    if (!lk.owns_lock()) lk.lock();
+    sh.waiters.fetch_sub(1, std::memory_order_relaxed);
+    return lk;
+  }
+
+  // s->eph_mu into the carry. The caller holds shard locks only (all earlier
+  // in the order), so this may block. Never two eph_mu at once.
+  static void carry_eph(Carry& k, Session* s, int* locks) {
+    if (k.eph == s) return;
+    k.drop_eph();
+    s->eph_mu.lock();
+    k.eph = s;
+    ++*locks;
+  }
+
   // ---------------- lifecycle ----------------
 
   void start() {
@@ -573,6 +743,11 @@ struct Ensemble::Impl {
     }
     loops.clear();
     for (size_t i = 0; i < io; i++) loops.push_back(std::make_unique<EventLoop>());
+    if (n_ops != io) {
+      // the pool's size follows from cfg alone, so a restart keeps its counts
+      ops = std::make_unique<OpCounters[]>(io);
+      n_ops = io;
+    }
     {
       std::lock_guard<std::mutex> g(admin_mu);
       servers.resize(n);
@@ -746,6 +921,18 @@ struct Ensemble::Impl {
 
   // returns false if the conn was closed
   bool process_frames(Conn* c) {
+    // the drain's carried locks: released by every op that is not a plain
+    // create/delete, by close_conn, and by this holder's destructor on every
+    // way out of the drain
+    struct CarryScope {
+      Conn* c;
+      Carry carry;
+      explicit CarryScope(Conn* cc) : c(cc) { c->carry = &carry; }
+      ~CarryScope() {
+        carry.release();
+        c->carry = nullptr;
+      }
+    } scope(c);
     while (!c->dead.load()) {
       size_t avail = c->inbuf.size();
       if (avail < 4) break;
@@ -784,9 +971,12 @@ struct Ensemble::Impl {
       RequestHeader hdr;
       hdr.deserialize(r);
       touch(c);
+      // only consecutive create / create2 / delete frames carry locks; every
+      // other op (unknown ones included) runs with nothing held
+      if (hdr.type != kOpCreate && hdr.type != kOpCreate2 && hdr.type != kOpDelete) c->carry->release();
       switch (hdr.type) {
         case kOpPing:
-          cnt(c).ping.fetch_add(1, std::memory_order_relaxed);
+          bump(cnt(c).ping);
           send_reply(c, kXidPing, zxid_counter.load(std::memory_order_relaxed), kZOk, nullptr);
           break;
         case kOpCreate:
@@ -836,16 +1026,18 @@ struct Ensemble::Impl {
           send_reply(c, hdr.xid, zxid_counter.load(std::memory_order_relaxed), kZOk, nullptr);
           break;
         default:
-          cnt(c).unknown.fetch_add(1, std::memory_order_relaxed);
+          bump(cnt(c).unknown);
           send_reply(c, hdr.xid, zxid_counter.load(std::memory_order_relaxed), kZSystemError, nullptr);
           break;
       }
       return true;
     } catch (const std::exception& e) {
+      c->carry->release();
       log.warn("ensemble: malformed frame, closing conn", {{"err", Json(e.what())}});
       return false;
     } catch (...) {
       // never unwind out of a drain: its staged replies would go unflushed
+      c->carry->release();
       return false;
     }
   }
@@ -853,7 +1045,7 @@ struct Ensemble::Impl {
   void handle_connect(Conn* c, JuteReader& r) {
     ConnectRequest req;
     req.deserialize(r);
-    cnt(c).connect.fetch_add(1, std::memory_order_relaxed);
+    bump(cnt(c).connect);
     ConnectResponse resp;
     resp.has_read_only = req.has_read_only;
     bool expired_handshake = false;
@@ -930,7 +1122,7 @@ struct Ensemble::Impl {
   // --- ops ---
 
   void handle_create(Conn* c, int32_t xid, JuteReader& r, bool with_stat = false) {
-    cnt(c).create.fetch_add(1, std::memory_order_relaxed);
+    bump(cnt(c).create);
     // parse in place: path and payload are views of the frame, which stays
     // put in c->inbuf for the whole drain. The ACL vector is validated and
     // skipped (the open-ACL server discards it).
@@ -949,14 +1141,21 @@ struct Ensemble::Impl {
     Stat created_stat;    // snapshot for create2 replies
     std::string seq_path;  // SEQUENCE only: the path with its suffix
     std::string_view final_path = path;
+    int locks = 0;  // mutexes this request took (tree_locks)
     if (!valid_path(path) || path == "/") {
       err = kZMarshallingError;
     } else {
       // one hash per path: it picks the shard and probes the map
       PathRef cref = ref_of(path);
       PathRef pref = parent_ref(c, parent_view(path));
-      TwoShardLock lk(*this, cref, pref);
-      Shard& psh = *lk.second;
+      // A SEQUENCE create carries nothing: it lets go of the drain's locks
+      // and runs under a carry of its own, which this scope releases.
+      Carry own_locks;
+      if (flags & kSequence) c->carry->release();
+      Carry& k = (flags & kSequence) ? own_locks : *c->carry;
+      Shard* first_csh = &shard_of(cref);
+      std::unique_lock<std::mutex> child_lk = acquire_for(k, cref.hash % kShards, pref.hash % kShards, &locks);
+      Shard& psh = shard_of(pref);
       ZNode* parp = psh.nodes.find(pref);
       if (!parp) {
         err = kZNoNode;
@@ -964,7 +1163,7 @@ struct Ensemble::Impl {
         err = kZNoChildrenForEphemerals;
       } else {
         ZNode& par = *parp;
-        Shard* csh = lk.first;
+        Shard* csh = first_csh;
         std::unique_lock<std::mutex> extra;
         if (flags & kSequence) {
           char suffix[16];
@@ -978,16 +1177,19 @@ struct Ensemble::Impl {
           // than the request path; lock it too in that (registrar-unused)
           // corner
           csh = &shard_of(cref);
-          if (csh != lk.first && csh != &psh) {
+          if (csh != first_csh && csh != &psh) {
             extra = std::unique_lock<std::mutex>(csh->mu, std::try_to_lock);
-            if (!extra.owns_lock()) err = kZSystemError;  // pathological shard collision
+            if (!extra.owns_lock())
+              err = kZSystemError;  // pathological shard collision
+            else
+              locks++;
           }
         }
         // Ephemeral creates and session death. kill_session clears `alive`
         // under eph_mu and only then drains the session's index, one node at
-        // a time, each pop under eph_mu again. We check `alive` and link the
-        // new node inside ONE eph_mu critical section (held across the
-        // insert), so exactly one of two things happens:
+        // a time, each pop under eph_mu again. We read `alive` and link the
+        // new node inside ONE eph_mu critical section, so exactly one of two
+        // things happens:
         //   - we saw alive: the node is in the index before the kill can
         //     take eph_mu to clear the flag, so the drain finds and removes
         //     it;
@@ -995,13 +1197,19 @@ struct Ensemble::Impl {
         //     SESSION_EXPIRED.
         // No ephemeral can therefore outlive its session, and unlike a
         // create-then-roll-back no half-registered node is ever visible.
-        // Lock order: shard(s) → eph_mu (kill_session holds eph_mu alone).
+        // The section is the drain's carried one: eph_mu is taken here if the
+        // carry does not hold it yet and stays held for the creates and
+        // deletes that follow, at most kCarryBound of them. `alive` is still
+        // read for EVERY ephemeral create, under the held mutex: a kill that
+        // is waiting for eph_mu has not cleared it yet, and one that got in
+        // between two carries is seen by the next read. The kill waits for at
+        // most one carry.
+        // Lock order: shard(s) → eph_mu (kill_session takes eph_mu alone).
         Session* owner = nullptr;
-        std::unique_lock<std::mutex> eg;
         if (err == kZOk && (flags & kEphemeral)) {
           owner = c->session.get();
           if (owner) {
-            eg = std::unique_lock<std::mutex>(owner->eph_mu);
+            carry_eph(k, owner, &locks);
             if (!owner->alive.load(std::memory_order_relaxed)) owner = nullptr;
           }
           if (!owner) err = kZSessionExpired;
@@ -1019,9 +1227,8 @@ struct Ensemble::Impl {
           n.stat.data_length = static_cast<int32_t>(data.size());
           if (owner) {
             n.stat.ephemeral_owner = sid;
-            n.owner = c->session;
+            n.owner = owner;
             eph_link(*owner, n);
-            eg.unlock();
           }
           link_child(par, n);
           par.stat.cversion++;
@@ -1033,6 +1240,7 @@ struct Ensemble::Impl {
         }
       }
     }
+    if (locks) bump(cnt(c).tree_locks, static_cast<uint64_t>(locks));
     // mutating replies carry the op's OWN zxid (a fresh counter read could
     // exceed what this client actually observed — ADVICE r1). The path goes
     // out straight from the request bytes (or the SEQUENCE path).
@@ -1047,18 +1255,20 @@ struct Ensemble::Impl {
   }
 
   void handle_delete(Conn* c, int32_t xid, JuteReader& r) {
-    cnt(c).del.fetch_add(1, std::memory_order_relaxed);
+    bump(cnt(c).del);
     std::string_view path = r.read_string_view();
     int32_t version = r.read_int();
     int32_t err = kZOk;
     int64_t op_zxid = 0;
+    int locks = 0;
     {
-      // one critical section: both shards locked once, checks and removal
-      // together
+      // one critical section: both shards locked (the parent's carried from
+      // the previous sibling where there was one), checks and removal together
       PathRef cref = ref_of(path);
       PathRef pref = parent_ref(c, parent_view(path));
-      TwoShardLock lk(*this, cref, pref);
-      Shard& csh = *lk.first;
+      Carry& k = *c->carry;
+      std::unique_lock<std::mutex> child_lk = acquire_for(k, cref.hash % kShards, pref.hash % kShards, &locks);
+      Shard& csh = shard_of(cref);
       ZNode* n = csh.nodes.find(cref);
       if (!n || path == "/") {
         err = kZNoNode;
@@ -1067,9 +1277,20 @@ struct Ensemble::Impl {
       } else if (version != -1 && version != n->stat.version) {
         err = kZBadVersion;
       } else {
-        op_zxid = remove_node_locked(csh, n, *lk.second);
+        // The node leaves its owner's index under that owner's eph_mu. Our
+        // own session's is carried (taken now if need be). Another
+        // session's is taken for this node alone, and the carried one is
+        // dropped first: two eph_mu are never held at once.
+        if (Session* o = n->owner) {
+          if (o == c->session.get())
+            carry_eph(k, o, &locks);
+          else
+            k.drop_eph();
+        }
+        op_zxid = remove_node_locked(csh, n, shard_of(pref), k.eph, &locks);
       }
     }
+    if (locks) bump(cnt(c).tree_locks, static_cast<uint64_t>(locks));
     send_reply(c, xid,
                op_zxid ? op_zxid : zxid_counter.load(std::memory_order_relaxed),
                err, nullptr);
@@ -1087,14 +1308,14 @@ struct Ensemble::Impl {
     ZNode* n = csh.nodes.find(cref);
     if (!n) return false;
     if (n->nchildren != 0 || n->parent == nullptr) return false;
-    if (only_owner && n->owner.get() != only_owner) return false;
+    if (only_owner && n->owner != only_owner) return false;
     int64_t z = remove_node_locked(csh, n, *lk.second);
     if (out_zxid) *out_zxid = z;
     return true;
   }
 
   void handle_exists(Conn* c, int32_t xid, JuteReader& r) {
-    cnt(c).exists.fetch_add(1, std::memory_order_relaxed);
+    bump(cnt(c).exists);
     std::string_view path = r.read_string_view();
     bool watch = r.read_bool();
     int32_t err = kZOk;
@@ -1102,7 +1323,8 @@ struct Ensemble::Impl {
     {
       PathRef ref = ref_of(path);
       Shard& sh = shard_of(ref);
-      std::lock_guard<std::mutex> lk(sh.mu);
+      std::unique_lock<std::mutex> lk = lock_shard(sh);
+      bump(cnt(c).tree_locks);
       if (watch) watch_set(sh.data_watches, ref).insert(sid_of(c));
       if (const ZNode* n = sh.nodes.find(ref))
         stat = n->stat;
@@ -1116,7 +1338,7 @@ struct Ensemble::Impl {
   }
 
   void handle_get_data(Conn* c, int32_t xid, JuteReader& r) {
-    cnt(c).get_data.fetch_add(1, std::memory_order_relaxed);
+    bump(cnt(c).get_data);
     std::string_view path = r.read_string_view();
     bool watch = r.read_bool();
     int32_t err = kZOk;
@@ -1124,7 +1346,8 @@ struct Ensemble::Impl {
     {
       PathRef ref = ref_of(path);
       Shard& sh = shard_of(ref);
-      std::lock_guard<std::mutex> lk(sh.mu);
+      std::unique_lock<std::mutex> lk = lock_shard(sh);
+      bump(cnt(c).tree_locks);
       if (const ZNode* n = sh.nodes.find(ref)) {
         if (watch) watch_set(sh.data_watches, ref).insert(sid_of(c));
         resp.data = n->data();
@@ -1141,7 +1364,7 @@ struct Ensemble::Impl {
   }
 
   void handle_set_data(Conn* c, int32_t xid, JuteReader& r) {
-    cnt(c).set_data.fetch_add(1, std::memory_order_relaxed);
+    bump(cnt(c).set_data);
     std::string_view path = r.read_string_view();
     std::string_view data = r.read_buffer_view();
     int32_t version = r.read_int();
@@ -1151,7 +1374,8 @@ struct Ensemble::Impl {
     {
       PathRef ref = ref_of(path);
       Shard& sh = shard_of(ref);
-      std::lock_guard<std::mutex> lk(sh.mu);
+      std::unique_lock<std::mutex> lk = lock_shard(sh);
+      bump(cnt(c).tree_locks);
       ZNode* n = sh.nodes.find(ref);
       if (!n) {
         err = kZNoNode;
@@ -1176,7 +1400,7 @@ struct Ensemble::Impl {
   }
 
   void handle_get_children(Conn* c, int32_t xid, JuteReader& r) {
-    cnt(c).get_children.fetch_add(1, std::memory_order_relaxed);
+    bump(cnt(c).get_children);
     std::string_view path = r.read_string_view();
     bool watch = r.read_bool();
     int32_t err = kZOk;
@@ -1184,7 +1408,8 @@ struct Ensemble::Impl {
     {
       PathRef ref = ref_of(path);
       Shard& sh = shard_of(ref);
-      std::lock_guard<std::mutex> lk(sh.mu);
+      std::unique_lock<std::mutex> lk = lock_shard(sh);
+      bump(cnt(c).tree_locks);
       if (const ZNode* n = sh.nodes.find(ref)) {
         if (watch) watch_set(sh.child_watches, ref).insert(sid_of(c));
         list_children(*n, &resp.children);
@@ -1201,7 +1426,7 @@ struct Ensemble::Impl {
 
   // getChildren2: children + the node's Stat (3.4+ clients use it by default)
   void handle_get_children2(Conn* c, int32_t xid, JuteReader& r) {
-    cnt(c).get_children.fetch_add(1, std::memory_order_relaxed);
+    bump(cnt(c).get_children);
     std::string_view path = r.read_string_view();
     bool watch = r.read_bool();
     int32_t err = kZOk;
@@ -1210,7 +1435,8 @@ struct Ensemble::Impl {
     {
       PathRef ref = ref_of(path);
       Shard& sh = shard_of(ref);
-      std::lock_guard<std::mutex> lk(sh.mu);
+      std::unique_lock<std::mutex> lk = lock_shard(sh);
+      bump(cnt(c).tree_locks);
       if (const ZNode* n = sh.nodes.find(ref)) {
         if (watch) watch_set(sh.child_watches, ref).insert(sid_of(c));
         list_children(*n, &resp.children);
@@ -1312,6 +1538,7 @@ struct Ensemble::Impl {
       std::vector<std::unique_lock<std::mutex>> locks;
       locks.reserve(idxs.size());
       for (size_t i : idxs) locks.emplace_back(shards[i].mu);
+      bump(cnt(c).tree_locks, locks.size());
 
       // ---- validate against tree + overlay of txn effects ----
       struct Overlay {
@@ -1423,7 +1650,7 @@ struct Ensemble::Impl {
           std::string parent(parent_view(mo.path));
           switch (mo.type) {
             case kOpCreate: {
-              cnt(c).create.fetch_add(1, std::memory_order_relaxed);
+              bump(cnt(c).create);
               int64_t zz = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
               txn_zxid = zz;
               PathRef cref = ref_of(mo.path);
@@ -1439,7 +1666,8 @@ struct Ensemble::Impl {
                   // same alive/link handshake as handle_create; a create
                   // that loses it is rolled back once the locks are released
                   std::lock_guard<std::mutex> eg(mine->eph_mu);
-                  n.owner = mine;
+                  bump(cnt(c).tree_locks);
+                  n.owner = mine.get();
                   if (mine->alive.load(std::memory_order_relaxed))
                     eph_link(*mine, n);
                   else
@@ -1458,14 +1686,14 @@ struct Ensemble::Impl {
               break;
             }
             case kOpDelete: {
-              cnt(c).del.fetch_add(1, std::memory_order_relaxed);
+              bump(cnt(c).del);
               int64_t zz = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
               txn_zxid = zz;
               PathRef cref = ref_of(mo.path);
               Shard& csh = shard_of(cref);
               if (ZNode* n = csh.nodes.find(cref)) {
                 // may be ANOTHER session's ephemeral: leaves its owner's index
-                detach_ephemeral(*n);
+                bump(cnt(c).tree_locks, static_cast<uint64_t>(detach_ephemeral(*n)));
                 if (ZNode* par = n->parent) {
                   unlink_child(*n);
                   par->stat.cversion++;
@@ -1480,7 +1708,7 @@ struct Ensemble::Impl {
               break;
             }
             case kOpSetData: {
-              cnt(c).set_data.fetch_add(1, std::memory_order_relaxed);
+              bump(cnt(c).set_data);
               int64_t zz = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
               txn_zxid = zz;
               if (ZNode* n = find_node(ref_of(mo.path))) {
@@ -1560,7 +1788,8 @@ struct Ensemble::Impl {
       {
         PathRef ref = ref_of(path);
         Shard& sh = shard_of(ref);
-        std::lock_guard<std::mutex> lk(sh.mu);
+        std::unique_lock<std::mutex> lk = lock_shard(sh);
+        bump(cnt(c).tree_locks);
         const ZNode* n = sh.nodes.find(ref);
         if (!n)
           fire_deleted = true;
@@ -1577,7 +1806,8 @@ struct Ensemble::Impl {
       {
         PathRef ref = ref_of(path);
         Shard& sh = shard_of(ref);
-        std::lock_guard<std::mutex> lk(sh.mu);
+        std::unique_lock<std::mutex> lk = lock_shard(sh);
+        bump(cnt(c).tree_locks);
         if (sh.nodes.find(ref))
           fire_created = true;  // appeared while the client was away
         else
@@ -1590,7 +1820,8 @@ struct Ensemble::Impl {
       {
         PathRef ref = ref_of(path);
         Shard& sh = shard_of(ref);
-        std::lock_guard<std::mutex> lk(sh.mu);
+        std::unique_lock<std::mutex> lk = lock_shard(sh);
+        bump(cnt(c).tree_locks);
         const ZNode* n = sh.nodes.find(ref);
         if (!n)
           fire_deleted = true;
@@ -1621,7 +1852,8 @@ struct Ensemble::Impl {
     {
       PathRef ref = ref_of(path);
       Shard& sh = shard_of(ref);
-      std::lock_guard<std::mutex> lk(sh.mu);
+      std::unique_lock<std::mutex> lk = lock_shard(sh);
+      bump(cnt(c).tree_locks);
       if (const ZNode* n = sh.nodes.find(ref))
         stat = n->stat;
       else
@@ -1645,7 +1877,8 @@ struct Ensemble::Impl {
     {
       PathRef ref = ref_of(path);
       Shard& sh = shard_of(ref);
-      std::lock_guard<std::mutex> lk(sh.mu);
+      std::unique_lock<std::mutex> lk = lock_shard(sh);
+      bump(cnt(c).tree_locks);
       if (ZNode* n = sh.nodes.find(ref)) {
         n->stat.aversion++;
         stat = n->stat;
@@ -1661,7 +1894,7 @@ struct Ensemble::Impl {
   }
 
   void handle_close_session(Conn* c, int32_t xid) {
-    cnt(c).close_session.fetch_add(1, std::memory_order_relaxed);
+    bump(cnt(c).close_session);
     int64_t sid = sid_of(c);
     {
       std::lock_guard<std::mutex> og(c->out_mu);
@@ -1675,7 +1908,15 @@ struct Ensemble::Impl {
 
   // Expire/close a session: remove ephemerals (firing watches), tombstone it,
   // optionally retire its connection. Lock discipline: session_mu alone, then
-  // eph_mu alone, then per-path shard locks via delete_node.
+  // eph_mu alone, then per-path shard locks via delete_node; it never holds
+  // two of them at once, so it blocks on each with nothing held, which the
+  // blocking rule (struct Carry) always allows. A drain of this session's
+  // connection may be carrying eph_mu: each wait here lasts at most one
+  // carry, kCarryBound requests. A caller on an IO loop (closeSession) has
+  // released its own carry first (handle_frame), or the eph_mu lock below
+  // would be a self-deadlock.
+  // `s` stays on this stack until the drain below is through: that is what
+  // lets ZNode::owner be a plain pointer (see there).
   void kill_session(int64_t sid, bool close_conn_too) {
     SessionPtr s;
     {
@@ -1841,7 +2082,7 @@ struct Ensemble::Impl {
           }
 
           // ownership
-          Session* owner = n->owner.get();
+          Session* owner = n->owner;
           bool linked = false;
           if (owner) {
             if (known.count(owner)) {
@@ -1900,7 +2141,7 @@ struct Ensemble::Impl {
           bad(name, "listed node is not in the table at its path");
           continue;
         }
-        if (n->owner.get() != s.get()) bad(name, "lists " + std::string(n->path()) + ", which has another owner");
+        if (n->owner != s.get()) bad(name, "lists " + std::string(n->path()) + ", which has another owner");
         if (!n->eph_linked) bad(name, "lists " + std::string(n->path()) + ", which is not marked linked");
       }
       if (len != s->eph_count)
@@ -2260,6 +2501,7 @@ struct Ensemble::Impl {
 
   // MUST run on the owner loop thread.
   void close_conn(Conn* c) {
+    if (c->carry) c->carry->release();  // closing mid-drain: nothing stays locked
     c->dead.store(true);
     {
       std::lock_guard<std::mutex> g(conns_mu);
@@ -2484,17 +2726,20 @@ int64_t Ensemble::zxid() const { return impl_->zxid_counter.load(); }
 
 std::map<std::string, uint64_t> Ensemble::counters() const {
   std::map<std::string, uint64_t> out;
-  for (const auto& o : impl_->ops) {  // sum over the per-loop blocks
-    out["connect"] += o.connect.load();
-    out["create"] += o.create.load();
-    out["delete"] += o.del.load();
-    out["exists"] += o.exists.load();
-    out["getData"] += o.get_data.load();
-    out["setData"] += o.set_data.load();
-    out["getChildren"] += o.get_children.load();
-    out["ping"] += o.ping.load();
-    out["closeSession"] += o.close_session.load();
-    out["unknown"] += o.unknown.load();
+  constexpr auto rlx = std::memory_order_relaxed;
+  for (size_t i = 0; i < impl_->n_ops; i++) {  // sum over the per-loop blocks
+    const auto& o = impl_->ops[i];
+    out["connect"] += o.connect.load(rlx);
+    out["create"] += o.create.load(rlx);
+    out["delete"] += o.del.load(rlx);
+    out["exists"] += o.exists.load(rlx);
+    out["getData"] += o.get_data.load(rlx);
+    out["setData"] += o.set_data.load(rlx);
+    out["getChildren"] += o.get_children.load(rlx);
+    out["ping"] += o.ping.load(rlx);
+    out["closeSession"] += o.close_session.load(rlx);
+    out["unknown"] += o.unknown.load(rlx);
+    out["tree_locks"] += o.tree_locks.load(rlx);
   }
   for (auto it = out.begin(); it != out.end();) {
     if (it->second == 0)

@@ -439,6 +439,9 @@ int main(int argc, char** argv) {
   const char* names[3] = {"ens-io", "zk-loop", "caller"};
   Sample s0[3], s1[3];
   uint64_t ens_reg_allocs = 0, ens_hb_allocs = 0;
+  // tree locks over the timed steps: read outside the sampled window (the
+  // counter map allocates on the calling thread)
+  auto c0 = ens.counters();
   for (int t = 0; t < 3; t++) s0[t] = sample(tids[t]);
   double t0 = now_s();
   for (int i = 0; i < steps; i++) {
@@ -450,6 +453,11 @@ int main(int argc, char** argv) {
   }
   double wall = now_s() - t0;
   for (int t = 0; t < 3; t++) s1[t] = sample(tids[t]);
+  auto c1 = ens.counters();
+  // every exists takes exactly one shard lock and the heartbeat is nothing
+  // but exists, so the rest of a step's locks belong to its register phase
+  double locks_step = static_cast<double>(c1["tree_locks"] - c0["tree_locks"]) / steps;
+  double locks_register = locks_step - static_cast<double>(c1["exists"] - c0["exists"]) / steps;
 #ifdef HOTPATH_PROF
   prof_disarm();
 #endif
@@ -484,6 +492,7 @@ int main(int argc, char** argv) {
             (s1[t].allocs - s0[t].allocs) / k, (s1[t].bytes - s0[t].bytes) / k);
   fprintf(stderr, "ens-io allocs by phase: register %.1f/step, heartbeat(exists) %.1f/step, delete-only %.1f/batch\n",
           ens_reg_allocs / k, ens_hb_allocs / k, ens_del_allocs / static_cast<double>(del_rounds));
+  fprintf(stderr, "tree locks: %.1f/step, of which register %.1f/step\n", locks_step, locks_register);
 
   printf("{\"tool\": \"hotpath\", \"znodes\": %d, \"steps\": %d, \"warmup\": %d, \"wall_ms_per_step\": %.4f", n,
          steps, warmup, wall / k * 1e3);
@@ -494,6 +503,7 @@ int main(int argc, char** argv) {
   printf(", \"ens_io_allocs_register_per_step\": %.1f, \"ens_io_allocs_heartbeat_per_step\": %.1f"
          ", \"ens_io_allocs_delete_per_batch\": %.1f",
          ens_reg_allocs / k, ens_hb_allocs / k, ens_del_allocs / static_cast<double>(del_rounds));
+  printf(", \"tree_locks_per_step\": %.1f, \"tree_locks_register_per_step\": %.1f", locks_step, locks_register);
   printf(", \"requests\": {\"create\": %llu, \"delete\": %llu, \"exists\": %llu}}\n",
          static_cast<unsigned long long>(counters["create"]), static_cast<unsigned long long>(counters["delete"]),
          static_cast<unsigned long long>(counters["exists"]));

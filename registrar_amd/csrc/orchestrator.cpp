@@ -243,10 +243,10 @@ bool Orchestrator::connect_and_register(bool initial) {
   }
   {
     std::lock_guard<std::mutex> g(mu_);
-    znodes_ = res.znodes;
+    znodes_ = res.znodes();
     down_ = false;
   }
-  emit({OrchEvent::Type::Register, initial ? "" : "re-register", res.znodes, 0});
+  emit({OrchEvent::Type::Register, initial ? "" : "re-register", res.znodes(), 0});
   return true;
 }
 
@@ -403,10 +403,10 @@ void Orchestrator::on_health_record(const HealthRecord& rec) {
   }
   {
     std::lock_guard<std::mutex> g(mu_);
-    znodes_ = res.znodes;
+    znodes_ = res.znodes();
     down_ = false;
   }
-  emit({OrchEvent::Type::Register, "health-recovery", res.znodes, 0});
+  emit({OrchEvent::Type::Register, "health-recovery", res.znodes(), 0});
 }
 
 std::vector<std::string> Orchestrator::znodes() const {

@@ -244,6 +244,11 @@ PreparedRegistration prepare_registration(const RegistrationConfig& cfg) {
   prep.heartbeat_nodes = prep.nodes;
   if (cfg.service) prep.heartbeat_nodes.push_back(prep.path);
   prep.heartbeat_tpl = zk::ZkClient::make_exists_template(prep.heartbeat_nodes);
+  {
+    auto reg = std::make_shared<std::vector<std::string>>(prep.nodes);
+    if (cfg.service && std::find(reg->begin(), reg->end(), prep.path) == reg->end()) reg->push_back(prep.path);
+    prep.registered_nodes = std::move(reg);
+  }
   return prep;
 }
 
@@ -382,28 +387,26 @@ RegisterResult register_prepared(zk::ZkClient& client, PreparedRegistration& pre
     }
   }
 
-  result.znodes = prep.nodes;
-
   // 5) registerService: persistent put of the service record at $path itself,
-  //    appended to the heartbeat node list (lib/register.js:45-75)
+  //    which the prepared list of registered nodes already ends with
+  //    (lib/register.js:45-75)
   if (cfg.service) {
     int rc = client.put(prep.path, prep.service_payload);
     if (rc != zk::kZOk) {
       result.rc = rc;
       result.error = std::string("registerService: put ") + prep.path + " failed: " + zk::error_name(rc);
       make_rlog().error("registerService: put failed", {{"err", Json(result.error)}});
-      result.znodes.clear();
       return result;
     }
-    if (std::find(result.znodes.begin(), result.znodes.end(), prep.path) == result.znodes.end())
-      result.znodes.push_back(prep.path);
     if (dbg) make_rlog().debug("registerService: done");
   }
 
+  // the result refers to the prepared list: no per-call copy of N strings
+  result.nodes = prep.registered_nodes;
   result.rc = zk::kZOk;
   if (dbg) {
     Json zn = Json::array();
-    for (const auto& n : result.znodes) zn.push_back(Json(n));
+    for (const auto& n : result.znodes()) zn.push_back(Json(n));
     make_rlog().debug("register: done", {{"znodes", std::move(zn)}});
   }
   return result;

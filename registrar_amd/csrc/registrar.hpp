@@ -23,6 +23,7 @@
 // xGMI-local peers.
 #pragma once
 
+#include <memory>
 #include <optional>
 #include <string>
 #include <vector>
@@ -89,10 +90,18 @@ Json build_service_record(const RegistrationConfig& cfg);
 // The znode list register() will create: $path/$hostname + reversed aliases.
 std::vector<std::string> build_node_list(const RegistrationConfig& cfg);
 
+using NodeList = std::shared_ptr<const std::vector<std::string>>;
+
 struct RegisterResult {
   int rc = 0;                        // zk::kZOk on success
   std::string error;                 // human-readable failure
-  std::vector<std::string> znodes;   // nodes to heartbeat (incl. service path)
+  // nodes to heartbeat (incl. service path): on success the prepared
+  // registration's own immutable list, shared, not copied; unset on failure
+  NodeList nodes;
+  const std::vector<std::string>& znodes() const {
+    static const std::vector<std::string> none;
+    return nodes ? *nodes : none;
+  }
 };
 
 // All the derived state a register() needs — node list, deduped mkdirp
@@ -116,6 +125,10 @@ struct PreparedRegistration {
   zk::ZkClient::BatchTemplate rest_tpl;       // wire_ops minus cleanup (settle path)
   zk::ZkClient::BatchTemplate heartbeat_tpl;  // exists over heartbeat_nodes
   std::vector<std::string> heartbeat_nodes;   // nodes (+ service path)
+  // what a successful register() reports: nodes, plus the service path when
+  // a service is configured and the path is not one of the nodes already.
+  // Built once here and never changed, so every result can share it.
+  NodeList registered_nodes;
 };
 
 PreparedRegistration prepare_registration(const RegistrationConfig& cfg);

@@ -12,7 +12,9 @@
 //     and aliases, so each cleans up and recreates the other's znodes (one of
 //     a pair by atomic swap, one by cleanup + create) while the chaos thread
 //     goes on expiring sessions. A register or heartbeat that loses to its
-//     peer there is expected and not counted.
+//     peer there is expected and not counted,
+//   - then a crossed-parents phase on a two-loop ensemble of its own (see
+//     crossed_phase): the locks a drain carries, under contention.
 // At the end, with every client closed and every session gone, the tree must
 // pass Ensemble::audit() and hold no ephemeral.
 // Exit code 0 = every cycle behaved and the end state is sound; sanitizers
@@ -72,6 +74,122 @@ void arm_watchdog(int seconds) {
     _exit(42);
   }).detach();
 }
+// Crossed-parents phase, on an ensemble of its own with two IO loops. Two
+// sessions, one per loop, pipeline batches of ephemeral creates and deletes
+// that alternate between their own parent and the other session's, so each
+// drain carries one parent's shard lock and the session's eph_mu while the
+// other loop wants them. A third thread reads through the public API, sends
+// exists through a client of its own and runs audit() all the while, and the
+// second session is expired half way. Returns true when every thread came back
+// and what is left is exactly the surviving session's last batch.
+bool crossed_phase(int seconds, const Logger& log) {
+  zk::EnsembleConfig ecfg;
+  ecfg.ports = {0};
+  ecfg.io_threads = 2;
+  ecfg.tick_ms = 50;
+  ecfg.log_level = LogLevel::Error;
+  zk::Ensemble ens(ecfg);
+  ens.start();
+  int port = ens.ports()[0];
+  auto make_client = [&] {
+    zk::ZkClientConfig ccfg;
+    ccfg.servers.push_back({"127.0.0.1", port});
+    ccfg.session_timeout_ms = 30000;
+    ccfg.log_level = LogLevel::Fatal;
+    auto c = std::make_unique<zk::ZkClient>(std::move(ccfg), log);
+    c->start();
+    return c;
+  };
+  // connections go to the loops round-robin: 0 and 1 land on different loops
+  std::unique_ptr<zk::ZkClient> cl[2] = {make_client(), nullptr};
+  if (!cl[0]->wait_connected(5000)) return false;
+  cl[1] = make_client();
+  if (!cl[1]->wait_connected(5000)) return false;
+  auto reader = make_client();
+  if (!reader->wait_connected(5000)) return false;
+  const std::string parent[2] = {"/x/p0", "/x/p1"};
+  if (cl[0]->mkdirp(parent[0]) != zk::kZOk || cl[0]->mkdirp(parent[1]) != zk::kZOk) return false;
+
+  constexpr int kBatch = 96;  // three carries' worth per parent switch pattern
+  auto batch_of = [&](int who) {
+    std::vector<std::string> paths;
+    for (int j = 0; j < kBatch; j++) {
+      // runs of 8 under one parent, then 8 under the other
+      int under = ((j / 8) % 2 == 0) ? who : 1 - who;
+      paths.push_back(parent[under] + "/s" + std::to_string(who) + "_" + std::to_string(j));
+    }
+    return paths;
+  };
+  std::atomic<bool> stop{false};
+  std::atomic<uint64_t> rounds[2] = {{0}, {0}};
+  std::atomic<int> bad{0};
+  auto worker = [&](int who) {
+    std::vector<std::string> paths = batch_of(who);
+    std::vector<std::string> datas(paths.size(), "crossed");
+    while (!stop.load() && cl[who]->state() == zk::SessionState::Connected) {
+      std::vector<int> rcs = cl[who]->create_many(paths, datas, zk::kEphemeral);
+      bool lost = false;
+      for (int rc : rcs) {
+        if (rc == zk::kZConnectionLoss || rc == zk::kZSessionExpired)
+          lost = true;
+        else if (rc != zk::kZOk)
+          bad.fetch_add(1);
+      }
+      if (lost) break;
+      rcs = cl[who]->delete_many(paths);
+      for (int rc : rcs) {
+        if (rc == zk::kZConnectionLoss || rc == zk::kZSessionExpired)
+          lost = true;
+        else if (rc == zk::kZNoNode && who == 1)
+          lost = true;  // the expiry's drain got to the node first
+        else if (rc != zk::kZOk)
+          bad.fetch_add(1);
+      }
+      if (lost) break;
+      rounds[who].fetch_add(1);
+    }
+  };
+  auto observer = [&] {
+    while (!stop.load()) {
+      for (int p = 0; p < 2; p++) {
+        reader->exists(parent[p]);
+        reader->exists(parent[p] + "/s" + std::to_string(p) + "_0");
+        ens.get(parent[p]);
+      }
+      ens.audit();  // mid-expiry findings are expected; it must only return
+    }
+  };
+  std::thread t0(worker, 0), t1(worker, 1), t2(observer);
+  std::this_thread::sleep_for(std::chrono::milliseconds(seconds * 500));
+  ens.expire_session(cl[1]->session_id());
+  std::this_thread::sleep_for(std::chrono::milliseconds(seconds * 500));
+  stop.store(true);
+  t0.join();
+  t1.join();
+  t2.join();
+
+  // the survivor leaves one last batch behind
+  std::vector<std::string> last = batch_of(0);
+  std::vector<int> rcs = cl[0]->create_many(last, std::vector<std::string>(last.size(), "last"), zk::kEphemeral);
+  bool ok = true;
+  for (int rc : rcs) ok = ok && rc == zk::kZOk;
+  size_t want[2] = {0, 0};
+  for (int j = 0; j < kBatch; j++) want[((j / 8) % 2 == 0) ? 0 : 1]++;
+  std::vector<std::string> violations = ens.audit();
+  size_t have0 = ens.children(parent[0]).size(), have1 = ens.children(parent[1]).size();
+  size_t eph = ens.ephemeral_count();
+  printf("stress: crossed phase: %llu + %llu rounds, %d unexpected rcs, %zu + %zu survivors, %zu ephemerals\n",
+         static_cast<unsigned long long>(rounds[0].load()), static_cast<unsigned long long>(rounds[1].load()),
+         bad.load(), have0, have1, eph);
+  for (const auto& v : violations) printf("stress: crossed phase: audit: %s\n", v.c_str());
+  ok = ok && violations.empty() && bad.load() == 0 && rounds[0].load() > 0 && have0 == want[0] &&
+       have1 == want[1] && eph == static_cast<size_t>(kBatch);
+  reader->close();
+  cl[0]->close();
+  cl[1]->close();
+  ens.stop();
+  return ok;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -86,6 +204,7 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[i], "-p") && i + 1 < argc) contested_seconds = atoi(argv[++i]);
   }
   if (contested_seconds < 0) contested_seconds = seconds / 2;
+  int crossed_secs = seconds > 0 ? std::max(2, seconds / 4) : 0;
 
   Logger log("stress");
   log.set_level(LogLevel::Error);
@@ -138,7 +257,7 @@ int main(int argc, char** argv) {
           break;
         }
         // arm some watches like a Binder reader would
-        client.exists(res.znodes[0], nullptr, true);
+        client.exists(res.znodes()[0], nullptr, true);
         std::vector<std::string> ch;
         client.get_children(domain_to_path(reg.domain), &ch, true);
         // exercise multi under chaos too: atomic delete+create of one node
@@ -146,11 +265,11 @@ int main(int argc, char** argv) {
           std::vector<zk::ZkClient::MixedOp> mops;
           zk::ZkClient::MixedOp d;
           d.op = zk::kOpDelete;
-          d.path = res.znodes[0];
+          d.path = res.znodes()[0];
           mops.push_back(d);
           zk::ZkClient::MixedOp cr;
           cr.op = zk::kOpCreate;
-          cr.path = res.znodes[0];
+          cr.path = res.znodes()[0];
           cr.data = "swap";
           cr.flags = zk::kEphemeral;
           mops.push_back(cr);
@@ -158,16 +277,16 @@ int main(int argc, char** argv) {
         }
         // setData past the node block's inline capacity and back (the node
         // stays put; its data moves out of line and in again)
-        client.set(res.znodes[0], std::string(6000, 'g'), -1, nullptr);
-        client.set(res.znodes[0], "small", -1, nullptr);
+        client.set(res.znodes()[0], std::string(6000, 'g'), -1, nullptr);
+        client.set(res.znodes()[0], "small", -1, nullptr);
         zk::RetryPolicy rp;
         rp.max_attempts = 1;
         rp.initial_delay_ms = 10;
-        int rc = client.heartbeat(res.znodes, rp, nullptr);
+        int rc = client.heartbeat(res.znodes(), rp, nullptr);
         // contested: the peer may have replaced or removed any of the nodes
         if (!contested && rc != zk::kZOk && rc != zk::kZConnectionLoss && rc != zk::kZSessionExpired)
           failures.fetch_add(1);
-        unregister_node(client, res.znodes, log);
+        unregister_node(client, res.znodes(), log);
         (contested ? contested_cycles : cycles).fetch_add(1);
       }
       client.close();
@@ -229,6 +348,9 @@ int main(int argc, char** argv) {
     chaos.join();
   }
 
+  // crossed parents (carried locks under contention), on its own ensemble
+  bool crossed_ok = crossed_secs <= 0 || crossed_phase(crossed_secs, log);
+
   // End state. Every client is closed, so every session ends: by its close,
   // or (where the close was lost to a killed server) by the expiry sweep. A
   // close is acknowledged before the ensemble has drained the session's
@@ -271,5 +393,6 @@ int main(int argc, char** argv) {
   // hard failures are register errors while connected — tolerate a few from
   // chaos timing, fail on systematic breakage
   bool behaved = cycles.load() > 0 && failures.load() < cycles.load() / 4 + 16;
-  return (behaved && sound) ? 0 : 1;
+  if (!crossed_ok) printf("stress: the crossed-parents phase failed\n");
+  return (behaved && sound && crossed_ok) ? 0 : 1;
 }
