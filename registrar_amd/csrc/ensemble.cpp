@@ -23,6 +23,8 @@
 // other lock held before taking shard locks (see the phase comments).
 #include "ensemble.hpp"
 
+#include "node_store.hpp"
+
 #include <arpa/inet.h>
 #include <fcntl.h>
 #include <netinet/in.h>
@@ -37,6 +39,9 @@
 
 namespace registrar {
 namespace zk {
+
+// paths, ZNode, NodeStore, Session and the link helpers (node_store.hpp)
+using namespace detail;
 
 namespace {
 
@@ -64,316 +69,31 @@ int64_t wall_ms() {
   return static_cast<int64_t>(ts.tv_sec) * 1000 + ts.tv_nsec / 1000000;
 }
 
-// Parent of a path as a view of the same bytes ("/" for depth-1 paths).
-std::string_view parent_view(std::string_view p) {
-  size_t pos = p.rfind('/');
-  if (pos == std::string_view::npos || pos == 0) return "/";
-  return p.substr(0, pos);
+// Write data[*off..len) to a non-blocking socket until it is all out, the
+// socket would block, or it fails; *off moves past what was written.
+enum class SendResult { kDone, kWouldBlock, kError };
+SendResult send_some(int fd, const char* data, size_t len, size_t* off) {
+  while (*off < len) {
+    ssize_t n = send(fd, data + *off, len - *off, MSG_NOSIGNAL);
+    if (n > 0)
+      *off += static_cast<size_t>(n);
+    else if (n < 0 && (errno == EAGAIN || errno == EWOULDBLOCK))
+      return SendResult::kWouldBlock;
+    else if (!(n < 0 && errno == EINTR))
+      return SendResult::kError;
+  }
+  return SendResult::kDone;
 }
-
-bool valid_path(std::string_view p) {
-  if (p.empty() || p[0] != '/') return false;
-  if (p.size() > 1 && p.back() == '/') return false;
-  if (p.find("//") != std::string_view::npos) return false;
-  return true;
-}
-
-// The node table and the watch maps are keyed by (path, hash of path). A
-// request hashes its path once: the same value picks the shard and probes the
-// table, and lookups go by view so no std::string is built to find a node.
-// A node's path lives once, inline in the node's block (NodeStore below); the
-// watch maps own their keys (PathKey, C++20 heterogeneous lookup).
-struct PathKey {
-  std::string path;
-  size_t hash;
-};
-struct PathRef {
-  std::string_view path;
-  size_t hash;
-};
-inline PathRef ref_of(std::string_view p) { return {p, std::hash<std::string_view>{}(p)}; }
-inline PathRef ref_of(const PathKey& k) { return {k.path, k.hash}; }
-struct PathHash {
-  using is_transparent = void;
-  size_t operator()(const PathKey& k) const noexcept { return k.hash; }
-  size_t operator()(const PathRef& r) const noexcept { return r.hash; }
-};
-struct PathEq {
-  using is_transparent = void;
-  bool operator()(const PathKey& a, const PathKey& b) const noexcept { return a.path == b.path; }
-  bool operator()(const PathKey& a, const PathRef& b) const noexcept { return a.path == b.path; }
-  bool operator()(const PathRef& a, const PathKey& b) const noexcept { return a.path == b.path; }
-};
 
 }  // namespace
 
 struct Ensemble::Impl {
   static constexpr size_t kShards = 64;
 
-  struct ZNode;
   struct Carry;
 
-  struct Session {
-    int64_t id = 0;
-    std::string passwd;
-    int timeout_ms = 30000;
-    std::atomic<int64_t> last_touch{0};  // monotonic ms, lock-free touch
-    std::atomic<uint64_t> conn_id{0};    // 0 = detached
-    // false once kill_session starts; written under eph_mu, so a create that
-    // reads it under eph_mu either links before the kill's drain or not at all
-    std::atomic<bool> alive{true};
-    std::mutex eph_mu;
-    // this session's ephemerals: intrusive list through ZNode::eph_prev/next
-    // (no per-create allocation, no second copy of the path)
-    ZNode* eph_head = nullptr;
-    size_t eph_count = 0;
-  };
   using SessionPtr = std::shared_ptr<Session>;
-
-  // A znode is ONE block: this header, then its path bytes, then its data
-  // bytes. Blocks never move, so the tree links nodes by pointer:
-  //   - hash / chain / path_len are the node's place in its shard's table
-  //     (shard lock); the path is immutable,
-  //   - first_child / nchildren and the children's parent / sib_prev /
-  //     sib_next are guarded by THIS node's shard lock (a child is only ever
-  //     created or removed with its parent's shard locked, and a node with
-  //     children cannot be removed),
-  //   - owner / eph_prev / eph_next / eph_linked are guarded by the owner
-  //     session's eph_mu (taken inside the shard locks: shard → eph_mu),
-  //   - data lives inline behind the path while it fits the block; a setData
-  //     that outgrows the block moves it to `ext`, a buffer this node owns
-  //     (the node itself stays where it is).
-  struct ZNode {
-    Stat stat;
-    uint64_t hash = 0;       // full hash of the path
-    ZNode* chain = nullptr;  // next node in the bucket
-    ZNode* parent = nullptr;
-    ZNode* first_child = nullptr;
-    ZNode* sib_prev = nullptr;
-    ZNode* sib_next = nullptr;
-    // Ephemeral owner (null for persistent nodes). A plain pointer: the node
-    // never keeps its session alive, the session outlives the node instead.
-    //   - handle_create sets it only after reading alive==true under eph_mu,
-    //     and links the node in that same section; a create that sees !alive
-    //     links nothing and sets nothing.
-    //   - kill_session holds the SessionPtr on its stack until its drain has
-    //     removed every node linked to the session: a linked node is in the
-    //     drain's list, and a node the drain has popped is deleted (by the
-    //     drain, or by another request that takes the node's shard lock
-    //     first) before the drain moves on, since both need that shard lock.
-    //   - handle_multi may set it on an unlinked node when the session died
-    //     mid-transaction; it keeps the SessionPtr on its stack until the
-    //     rollback has removed that node (same shard-lock argument).
-    //   - until kill_session runs, `sessions` holds the session.
-    // It is dereferenced only with the node's shard locked, i.e. while the
-    // node is in the table. Teardown (~NodeStore, release) never reads it.
-    Session* owner = nullptr;
-    ZNode* eph_prev = nullptr;
-    ZNode* eph_next = nullptr;
-    char* ext = nullptr;     // out-of-line data, null while the data is inline
-    uint32_t path_len = 0;
-    uint32_t data_len = 0;
-    uint32_t inline_cap = 0;  // bytes behind the header (path + inline data)
-    uint32_t ext_cap = 0;
-    int32_t nchildren = 0;
-    uint8_t size_class = 0;  // kNoClass: block was sized exactly, never cached
-    bool eph_linked = false;
-
-    char* tail() { return reinterpret_cast<char*>(this) + sizeof(ZNode); }
-    const char* tail() const { return reinterpret_cast<const char*>(this) + sizeof(ZNode); }
-    std::string_view path() const { return {tail(), path_len}; }
-    PathRef ref() const { return {path(), static_cast<size_t>(hash)}; }
-    std::string_view data() const { return {ext ? ext : tail() + path_len, data_len}; }
-    std::string_view name() const {
-      std::string_view p = path();
-      return p.substr(p.rfind('/') + 1);
-    }
-
-    void set_data(std::string_view d) {
-      if (d.size() <= inline_cap - path_len) {
-        if (ext) {
-          ::operator delete(ext);
-          ext = nullptr;
-          ext_cap = 0;
-        }
-        if (!d.empty()) memcpy(tail() + path_len, d.data(), d.size());
-      } else {
-        if (d.size() > ext_cap) {
-          char* nb = static_cast<char*>(::operator new(d.size()));
-          if (ext) ::operator delete(ext);
-          ext = nb;
-          ext_cap = static_cast<uint32_t>(d.size());
-        }
-        memcpy(ext, d.data(), d.size());
-      }
-      data_len = static_cast<uint32_t>(d.size());
-    }
-  };
-
-  // Block size classes (header + path + data, rounded up). The registrar's
-  // own nodes (a ~25-byte path, a ~100-byte JSON record) land in the second.
-  static constexpr size_t kBlockClasses[] = {256, 384, 512, 768, 1024, 1536, 2048, 4096};
-  static constexpr size_t kNumClasses = sizeof(kBlockClasses) / sizeof(kBlockClasses[0]);
-  static constexpr uint8_t kNoClass = 0xFF;
-  // Most released blocks a shard keeps per class. A re-register cycle at 8
-  // ranks x 1000 nodes frees, then re-creates, ~125 blocks per shard at
-  // uniform hashing; 256 covers that with room for skew. Retained at most:
-  // 64 shards x 256 x 384 bytes = ~6 MB for the class the registrar uses
-  // (~174 MB only if every class of every shard fills).
-  static constexpr size_t kMaxCachedPerClass = 256;
-  static_assert(sizeof(ZNode) < kBlockClasses[0], "smallest class must hold a header");
-
   using WatchMap = std::unordered_map<PathKey, std::set<int64_t>, PathHash, PathEq>;
-
-  // One shard's nodes: an intrusive chained hash table (power-of-two bucket
-  // array of ZNode*, the chain link and the full hash live in the node) plus
-  // the shard's free lists of released blocks. Everything here is guarded by
-  // the shard's mutex. Growth relinks nodes and never moves them.
-  struct NodeStore {
-    ZNode** buckets = nullptr;
-    size_t nbuckets = 0;  // power of two
-    size_t count = 0;
-
-    // INVARIANT: a block goes onto a free list only after its node has left
-    // the hash chain, its parent's sibling list and its owner's ephemeral
-    // list (release() asserts the last two; erase() does the first), and no
-    // ZNode* is dereferenced outside the lock that guards the link it was
-    // read through. A recycled block is worse than a freed one: a stale
-    // pointer would read a live, different node and no sanitizer would see it.
-    struct FreeBlock {
-      FreeBlock* next;
-    };
-    FreeBlock* free_head[kNumClasses] = {};
-    size_t free_count[kNumClasses] = {};
-    size_t cached = 0;  // sum of free_count
-
-    NodeStore() = default;
-    NodeStore(const NodeStore&) = delete;
-    NodeStore& operator=(const NodeStore&) = delete;
-
-    ~NodeStore() {
-      for (size_t b = 0; b < nbuckets; b++) {
-        for (ZNode* n = buckets[b]; n;) {
-          ZNode* next = n->chain;
-          if (n->ext) ::operator delete(n->ext);
-          n->~ZNode();
-          ::operator delete(n);
-          n = next;
-        }
-      }
-      ::operator delete(buckets);
-      for (size_t c = 0; c < kNumClasses; c++) {
-        for (FreeBlock* f = free_head[c]; f;) {
-          FreeBlock* next = f->next;
-          ::operator delete(f);
-          f = next;
-        }
-      }
-    }
-
-    size_t size() const { return count; }
-
-    // The shard index is hash % kShards (the low 6 bits), so the bucket index
-    // takes its bits from further up.
-    size_t bucket_of(uint64_t h) const { return (h >> 8) & (nbuckets - 1); }
-
-    ZNode* find(const PathRef& r) const {
-      if (nbuckets == 0) return nullptr;
-      for (ZNode* n = buckets[bucket_of(r.hash)]; n; n = n->chain) {
-        // the stored hash settles nearly every chain step without touching
-        // the path bytes
-        if (n->hash == r.hash && n->path_len == r.path.size() &&
-            memcmp(n->tail(), r.path.data(), r.path.size()) == 0)
-          return n;
-      }
-      return nullptr;
-    }
-
-    void grow() {
-      size_t nn = nbuckets ? nbuckets * 2 : 16;
-      ZNode** nb = static_cast<ZNode**>(::operator new(nn * sizeof(ZNode*)));
-      memset(nb, 0, nn * sizeof(ZNode*));
-      ZNode** old = buckets;
-      size_t on = nbuckets;
-      buckets = nb;
-      nbuckets = nn;
-      for (size_t b = 0; b < on; b++) {
-        for (ZNode* n = old[b]; n;) {
-          ZNode* next = n->chain;
-          size_t i = bucket_of(n->hash);
-          n->chain = buckets[i];
-          buckets[i] = n;
-          n = next;
-        }
-      }
-      ::operator delete(old);
-    }
-
-    static uint8_t class_for(size_t bytes) {
-      for (size_t c = 0; c < kNumClasses; c++)
-        if (bytes <= kBlockClasses[c]) return static_cast<uint8_t>(c);
-      return kNoClass;
-    }
-
-    // A new node for r (which must not be in the table) holding `data`:
-    // exactly one block, from the free list of its class when there is one.
-    ZNode* create(const PathRef& r, std::string_view data) {
-      if (count >= nbuckets) grow();
-      size_t need = sizeof(ZNode) + r.path.size() + data.size();
-      uint8_t cls = class_for(need);
-      size_t bytes = cls == kNoClass ? need : kBlockClasses[cls];
-      void* mem;
-      if (cls != kNoClass && free_head[cls]) {
-        FreeBlock* f = free_head[cls];
-        free_head[cls] = f->next;
-        free_count[cls]--;
-        cached--;
-        mem = f;
-      } else {
-        mem = ::operator new(bytes);
-      }
-      ZNode* n = new (mem) ZNode();
-      n->hash = r.hash;
-      n->size_class = cls;
-      n->path_len = static_cast<uint32_t>(r.path.size());
-      n->inline_cap = static_cast<uint32_t>(bytes - sizeof(ZNode));
-      n->data_len = static_cast<uint32_t>(data.size());
-      memcpy(n->tail(), r.path.data(), r.path.size());
-      if (!data.empty()) memcpy(n->tail() + r.path.size(), data.data(), data.size());
-      size_t i = bucket_of(r.hash);
-      n->chain = buckets[i];
-      buckets[i] = n;
-      count++;
-      return n;
-    }
-
-    // Take n out of the table and release its block (and its out-of-line
-    // data). The caller has already unlinked it from its parent and from its
-    // owner's ephemeral list — see the invariant above.
-    void erase(ZNode* n) {
-      ZNode** pp = &buckets[bucket_of(n->hash)];
-      while (*pp != n) pp = &(*pp)->chain;
-      *pp = n->chain;
-      count--;
-      release(n);
-    }
-
-    void release(ZNode* n) {
-      if (n->parent || n->eph_linked || n->first_child) std::abort();  // invariant
-      if (n->ext) ::operator delete(n->ext);
-      uint8_t cls = n->size_class;
-      n->~ZNode();
-      if (cls != kNoClass && free_count[cls] < kMaxCachedPerClass) {
-        FreeBlock* f = reinterpret_cast<FreeBlock*>(n);
-        f->next = free_head[cls];
-        free_head[cls] = f;
-        free_count[cls]++;
-        cached++;
-      } else {
-        ::operator delete(n);
-      }
-    }
-  };
 
   struct Shard {
     std::mutex mu;
@@ -564,93 +284,110 @@ struct Ensemble::Impl {
   // the node at r in whichever shard r hashes to, or null
   ZNode* find_node(const PathRef& r) { return shard_of(r).nodes.find(r); }
 
-  static void link_child(ZNode& par, ZNode& ch) {
-    ch.parent = &par;
-    ch.sib_prev = nullptr;
-    ch.sib_next = par.first_child;
-    if (par.first_child) par.first_child->sib_prev = &ch;
-    par.first_child = &ch;
-    par.nchildren++;
+  // The mutations below are the only code that writes a znode's Stat (setACL's
+  // aversion aside) or changes a link. The single-op handlers and multi's
+  // apply phase both go through them. They mutate only: the caller holds the
+  // shard locks of the node and of its parent, and fires the watches.
+
+  // the only place a zxid is spent
+  int64_t next_zxid() { return zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1; }
+  // what a reply that committed nothing reports
+  int64_t last_zxid() const { return zxid_counter.load(std::memory_order_relaxed); }
+
+  // A new node at cref (validated absent) under par, committed at zxid z: one
+  // block for header, path and payload, linked into par's children.
+  static ZNode& insert_node(Shard& csh, const PathRef& cref, std::string_view data, ZNode& par, int64_t z,
+                            int64_t wall) {
+    ZNode& n = *csh.nodes.create(cref, data);
+    n.stat.czxid = z;
+    n.stat.mzxid = z;
+    n.stat.ctime = wall;
+    n.stat.mtime = wall;
+    n.stat.data_length = static_cast<int32_t>(data.size());
+    link_child(par, n);
+    child_list_changed(par, z);
+    return n;
   }
 
-  static void unlink_child(ZNode& ch) {
-    ZNode* par = ch.parent;
-    if (!par) return;
-    if (ch.sib_prev)
-      ch.sib_prev->sib_next = ch.sib_next;
-    else
-      par->first_child = ch.sib_next;
-    if (ch.sib_next) ch.sib_next->sib_prev = ch.sib_prev;
-    par->nchildren--;
-    ch.parent = ch.sib_prev = ch.sib_next = nullptr;
+  // par gained or lost a child at zxid z
+  static void child_list_changed(ZNode& par, int64_t z) {
+    par.stat.cversion++;
+    par.stat.pzxid = z;
+    par.stat.num_children = par.nchildren;
   }
 
-  // sorted child names (listings sort on demand; create/delete are O(1))
-  static void list_children(const ZNode& n, std::vector<std::string>* out) {
-    out->clear();
-    out->reserve(static_cast<size_t>(n.nchildren));
-    for (const ZNode* c = n.first_child; c; c = c->sib_next) out->emplace_back(c->name());
-    std::sort(out->begin(), out->end());
+  // Make the fresh node n an ephemeral of s; the caller holds s.eph_mu and
+  // passes what it read from s.alive inside that same critical section.
+  //
+  // Ephemeral creates and session death. kill_session clears `alive`
+  // under eph_mu and only then drains the session's index, one node at
+  // a time, each pop under eph_mu again. A create reads `alive` and links
+  // the new node inside ONE eph_mu critical section, so exactly one of two
+  // things happens:
+  //   - it saw alive: the node is in the index before the kill can
+  //     take eph_mu to clear the flag, so the drain finds and removes
+  //     it;
+  //   - it saw !alive: the node is not linked, and must not stay.
+  // handle_create reads `alive` before it inserts: on !alive nothing is
+  // inserted and the create fails with SESSION_EXPIRED, so unlike a
+  // create-then-roll-back no half-registered node is ever visible. Its
+  // section is the drain's carried one: eph_mu is taken if the
+  // carry does not hold it yet and stays held for the creates and
+  // deletes that follow, at most kCarryBound of them. `alive` is still
+  // read for EVERY ephemeral create, under the held mutex: a kill that
+  // is waiting for eph_mu has not cleared it yet, and one that got in
+  // between two carries is seen by the next read. The kill waits for at
+  // most one carry.
+  // handle_multi has inserted already (a transaction applies whole) and takes
+  // eph_mu per node: on !alive it sets the owner on the unlinked node and
+  // rolls that node back once the shard locks are released.
+  // No ephemeral can therefore outlive its session.
+  // Lock order: shard(s) → eph_mu (kill_session takes eph_mu alone).
+  static void own_ephemeral(ZNode& n, Session& s, bool alive) {
+    n.stat.ephemeral_owner = s.id;
+    n.owner = &s;
+    if (alive) eph_link(s, n);
   }
 
-  // s.eph_mu held
-  static void eph_link(Session& s, ZNode& n) {
-    n.eph_prev = nullptr;
-    n.eph_next = s.eph_head;
-    if (s.eph_head) s.eph_head->eph_prev = &n;
-    s.eph_head = &n;
-    n.eph_linked = true;
-    s.eph_count++;
-  }
-
-  // s.eph_mu held
-  static void eph_unlink(Session& s, ZNode& n) {
-    if (!n.eph_linked) return;
-    if (n.eph_prev)
-      n.eph_prev->eph_next = n.eph_next;
-    else
-      s.eph_head = n.eph_next;
-    if (n.eph_next) n.eph_next->eph_prev = n.eph_prev;
-    n.eph_prev = n.eph_next = nullptr;
-    n.eph_linked = false;
-    s.eph_count--;
-  }
-
-  // Take a node that is about to be erased out of its owner's ephemeral
-  // index. Runs inside the node's shard lock, BEFORE the erase: the index
-  // holds node pointers, so a node must never be freed (or, worse, recycled)
-  // while linked.
-  // `held`: the session whose eph_mu the caller holds already (a drain's
-  // carry), or null. Returns the number of mutexes it took.
-  static int detach_ephemeral(ZNode& n, Session* held = nullptr) {
-    if (!n.owner) return 0;
-    if (n.owner == held) {
-      eph_unlink(*n.owner, n);
-      return 0;
+  // Take n (no children) out of its owner's ephemeral index and out of its
+  // parent's children, at zxid z; returns the parent. Runs inside the node's
+  // shard lock, BEFORE the erase: the index holds node pointers, so a node
+  // must never be freed (or, worse, recycled) while linked.
+  // `eph_held`: the session whose eph_mu the caller holds already (a drain's
+  // carry), or null; *locks grows by the number of mutexes taken here.
+  static ZNode* detach_node(ZNode& n, int64_t z, Session* eph_held, int* locks) {
+    if (Session* o = n.owner) {
+      if (o == eph_held) {
+        eph_unlink(*o, n);
+      } else {
+        std::lock_guard<std::mutex> eg(o->eph_mu);
+        eph_unlink(*o, n);
+        ++*locks;
+      }
     }
-    std::lock_guard<std::mutex> eg(n.owner->eph_mu);
-    eph_unlink(*n.owner, n);
-    return 1;
+    ZNode* par = n.parent;
+    if (par) {
+      unlink_child(n);
+      child_list_changed(*par, z);
+    }
+    return par;
+  }
+
+  static void apply_set_data(ZNode& n, std::string_view data, int64_t z, int64_t wall) {
+    n.set_data(data);  // in place while it fits; the node never moves
+    n.stat.mzxid = z;
+    n.stat.mtime = wall;
+    n.stat.version++;
+    n.stat.data_length = static_cast<int32_t>(data.size());
   }
 
   // Remove node n (no children; its shard csh and its parent's shard psh
-  // both locked): session index, parent link + parent Stat, watches
-  // (parent's child watch first, then NodeDeleted), erase. Returns the zxid
-  // the removal committed at.
-  int64_t remove_node_locked(Shard& csh, ZNode* np, Shard& psh, Session* eph_held = nullptr,
-                             int* locks_taken = nullptr) {
-    ZNode& n = *np;
-    int64_t z = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
-    int took = detach_ephemeral(n, eph_held);
-    if (locks_taken) *locks_taken += took;
-    if (ZNode* par = n.parent) {
-      unlink_child(n);
-      par->stat.cversion++;
-      par->stat.pzxid = z;
-      par->stat.num_children = par->nchildren;
-      fire_child_watches_locked(psh, par->ref());
-    }
-    fire_deleted_watches_locked(csh, n.ref());  // n's own path bytes: before the erase
+  // both locked): detach, watches (parent's child watch first, then
+  // NodeDeleted), erase. Returns the zxid the removal committed at.
+  int64_t remove_node_locked(Shard& csh, ZNode* np, Shard& psh, Session* eph_held, int* locks) {
+    int64_t z = next_zxid();
+    if (ZNode* par = detach_node(*np, z, eph_held, locks)) fire_child_watches_locked(psh, par->ref());
+    fire_deleted_watches_locked(csh, np->ref());  // n's own path bytes: before the erase
     csh.nodes.erase(np);
     return z;
   }
@@ -718,6 +455,18 @@ struct Ensemble::Impl {
     if (!lk.owns_lock()) lk.lock();
     sh.waiters.fetch_sub(1, std::memory_order_relaxed);
     return lk;
+  }
+
+  // The one-path ops: hash the path once, lock its shard, look the node up,
+  // and run fn(shard, ref, node-or-null) under that lock (one tree_locks).
+  // Returns what fn returns, with the lock released.
+  template <typename Fn>
+  auto with_node(Conn* c, std::string_view path, Fn fn) {
+    PathRef ref = ref_of(path);
+    Shard& sh = shard_of(ref);
+    std::unique_lock<std::mutex> lk = lock_shard(sh);
+    bump(cnt(c).tree_locks);
+    return fn(sh, ref, sh.nodes.find(ref));
   }
 
   // s->eph_mu into the carry. The caller holds shard locks only (all earlier
@@ -977,7 +726,7 @@ struct Ensemble::Impl {
       switch (hdr.type) {
         case kOpPing:
           bump(cnt(c).ping);
-          send_reply(c, kXidPing, zxid_counter.load(std::memory_order_relaxed), kZOk, nullptr);
+          send_ack(c, kXidPing);
           break;
         case kOpCreate:
           handle_create(c, hdr.xid, r);
@@ -1006,8 +755,8 @@ struct Ensemble::Impl {
         case kOpSetACL:
           handle_set_acl(c, hdr.xid, r);
           break;
-        case kOpGetChildren2:
-          handle_get_children2(c, hdr.xid, r);
+        case kOpGetChildren2:  // children + the node's Stat (3.4+ clients use it by default)
+          handle_get_children(c, hdr.xid, r, /*with_stat=*/true);
           break;
         case kOpSync:
           handle_sync(c, hdr.xid, r);
@@ -1021,13 +770,13 @@ struct Ensemble::Impl {
         case kOpCloseSession:
           handle_close_session(c, hdr.xid);
           break;
-        case 100:  // auth packet (xid -4): ACLs are open here, ack and ignore
-                   // so real third-party clients that always send auth work
-          send_reply(c, hdr.xid, zxid_counter.load(std::memory_order_relaxed), kZOk, nullptr);
+        case kOpAuth:  // auth packet (xid -4): ACLs are open here, ack and ignore
+                       // so real third-party clients that always send auth work
+          send_ack(c, hdr.xid);
           break;
         default:
           bump(cnt(c).unknown);
-          send_reply(c, hdr.xid, zxid_counter.load(std::memory_order_relaxed), kZSystemError, nullptr);
+          send_error(c, hdr.xid, kZSystemError);
           break;
       }
       return true;
@@ -1136,7 +885,6 @@ struct Ensemble::Impl {
     }
     int32_t flags = r.read_int();
     int32_t err = kZOk;
-    int64_t sid = sid_of(c);
     int64_t op_zxid = 0;  // the zxid THIS create committed at
     Stat created_stat;    // snapshot for create2 replies
     std::string seq_path;  // SEQUENCE only: the path with its suffix
@@ -1185,26 +933,8 @@ struct Ensemble::Impl {
               locks++;
           }
         }
-        // Ephemeral creates and session death. kill_session clears `alive`
-        // under eph_mu and only then drains the session's index, one node at
-        // a time, each pop under eph_mu again. We read `alive` and link the
-        // new node inside ONE eph_mu critical section, so exactly one of two
-        // things happens:
-        //   - we saw alive: the node is in the index before the kill can
-        //     take eph_mu to clear the flag, so the drain finds and removes
-        //     it;
-        //   - we saw !alive: nothing is inserted and the create fails with
-        //     SESSION_EXPIRED.
-        // No ephemeral can therefore outlive its session, and unlike a
-        // create-then-roll-back no half-registered node is ever visible.
-        // The section is the drain's carried one: eph_mu is taken here if the
-        // carry does not hold it yet and stays held for the creates and
-        // deletes that follow, at most kCarryBound of them. `alive` is still
-        // read for EVERY ephemeral create, under the held mutex: a kill that
-        // is waiting for eph_mu has not cleared it yet, and one that got in
-        // between two carries is seen by the next read. The kill waits for at
-        // most one carry.
-        // Lock order: shard(s) → eph_mu (kill_session takes eph_mu alone).
+        // an ephemeral is created only while its session is seen alive under
+        // the carried eph_mu (own_ephemeral has the argument)
         Session* owner = nullptr;
         if (err == kZOk && (flags & kEphemeral)) {
           owner = c->session.get();
@@ -1216,24 +946,9 @@ struct Ensemble::Impl {
         }
         if (err == kZOk && csh->nodes.find(cref)) err = kZNodeExists;
         if (err == kZOk) {
-          int64_t zz = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
-          op_zxid = zz;
-          // one block for header, path and payload
-          ZNode& n = *csh->nodes.create(cref, data);
-          n.stat.czxid = zz;
-          n.stat.mzxid = zz;
-          n.stat.ctime = c->drain_wall_ms;
-          n.stat.mtime = n.stat.ctime;
-          n.stat.data_length = static_cast<int32_t>(data.size());
-          if (owner) {
-            n.stat.ephemeral_owner = sid;
-            n.owner = owner;
-            eph_link(*owner, n);
-          }
-          link_child(par, n);
-          par.stat.cversion++;
-          par.stat.pzxid = zz;
-          par.stat.num_children = par.nchildren;
+          op_zxid = next_zxid();
+          ZNode& n = insert_node(*csh, cref, data, par, op_zxid, c->drain_wall_ms);
+          if (owner) own_ephemeral(n, *owner, /*alive=*/true);
           fire_data_watches_locked(*csh, cref, kEventNodeCreated);
           fire_child_watches_locked(psh, pref);
           created_stat = n.stat;
@@ -1244,14 +959,11 @@ struct Ensemble::Impl {
     // mutating replies carry the op's OWN zxid (a fresh counter read could
     // exceed what this client actually observed — ADVICE r1). The path goes
     // out straight from the request bytes (or the SEQUENCE path).
-    if (err == kZOk)
-      send_fixed_reply(
-          c, xid, op_zxid, 4 + final_path.size() + (with_stat ? Stat::kWireSize : 0), [&](auto& w) {
-            w.write_string(final_path);                // CreateResponse
-            if (with_stat) created_stat.serialize(w);  // Create2Response
-          });
-    else
-      send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), err, nullptr);
+    if (err != kZOk) return send_error(c, xid, err);
+    send_fixed_reply(c, xid, op_zxid, 4 + final_path.size() + (with_stat ? Stat::kWireSize : 0), [&](auto& w) {
+      w.write_string(final_path);                // CreateResponse
+      if (with_stat) created_stat.serialize(w);  // Create2Response
+    });
   }
 
   void handle_delete(Conn* c, int32_t xid, JuteReader& r) {
@@ -1291,9 +1003,7 @@ struct Ensemble::Impl {
       }
     }
     if (locks) bump(cnt(c).tree_locks, static_cast<uint64_t>(locks));
-    send_reply(c, xid,
-               op_zxid ? op_zxid : zxid_counter.load(std::memory_order_relaxed),
-               err, nullptr);
+    send_reply(c, xid, op_zxid ? op_zxid : last_zxid(), err, nullptr);
   }
 
   // Full node removal for the callers that have only a path (session kill,
@@ -1309,7 +1019,8 @@ struct Ensemble::Impl {
     if (!n) return false;
     if (n->nchildren != 0 || n->parent == nullptr) return false;
     if (only_owner && n->owner != only_owner) return false;
-    int64_t z = remove_node_locked(csh, n, *lk.second);
+    int locks = 0;  // not a request handler: nothing counts them
+    int64_t z = remove_node_locked(csh, n, *lk.second, nullptr, &locks);
     if (out_zxid) *out_zxid = z;
     return true;
   }
@@ -1318,49 +1029,31 @@ struct Ensemble::Impl {
     bump(cnt(c).exists);
     std::string_view path = r.read_string_view();
     bool watch = r.read_bool();
-    int32_t err = kZOk;
     Stat stat;
-    {
-      PathRef ref = ref_of(path);
-      Shard& sh = shard_of(ref);
-      std::unique_lock<std::mutex> lk = lock_shard(sh);
-      bump(cnt(c).tree_locks);
+    int32_t err = with_node(c, path, [&](Shard& sh, const PathRef& ref, const ZNode* n) {
+      // the watch registers even on a missing node: that is what it waits for
       if (watch) watch_set(sh.data_watches, ref).insert(sid_of(c));
-      if (const ZNode* n = sh.nodes.find(ref))
-        stat = n->stat;
-      else
-        err = kZNoNode;
-    }
-    if (err == kZOk)
-      send_stat_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), stat);
-    else
-      send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), err, nullptr);
+      if (!n) return kZNoNode;
+      stat = n->stat;
+      return kZOk;
+    });
+    if (err != kZOk) return send_error(c, xid, err);
+    send_stat_reply(c, xid, last_zxid(), stat);
   }
 
   void handle_get_data(Conn* c, int32_t xid, JuteReader& r) {
     bump(cnt(c).get_data);
     std::string_view path = r.read_string_view();
     bool watch = r.read_bool();
-    int32_t err = kZOk;
     GetDataResponse resp;
-    {
-      PathRef ref = ref_of(path);
-      Shard& sh = shard_of(ref);
-      std::unique_lock<std::mutex> lk = lock_shard(sh);
-      bump(cnt(c).tree_locks);
-      if (const ZNode* n = sh.nodes.find(ref)) {
-        if (watch) watch_set(sh.data_watches, ref).insert(sid_of(c));
-        resp.data = n->data();
-        resp.stat = n->stat;
-      } else {
-        err = kZNoNode;
-      }
-    }
-    if (err == kZOk)
-      send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), kZOk,
-                 [&](JuteWriter& w) { resp.serialize(w); });
-    else
-      send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), err, nullptr);
+    int32_t err = with_node(c, path, [&](Shard& sh, const PathRef& ref, const ZNode* n) {
+      if (!n) return kZNoNode;
+      if (watch) watch_set(sh.data_watches, ref).insert(sid_of(c));
+      resp.data = n->data();
+      resp.stat = n->stat;
+      return kZOk;
+    });
+    send_reply(c, xid, last_zxid(), err, [&](JuteWriter& w) { resp.serialize(w); });
   }
 
   void handle_set_data(Conn* c, int32_t xid, JuteReader& r) {
@@ -1368,90 +1061,39 @@ struct Ensemble::Impl {
     std::string_view path = r.read_string_view();
     std::string_view data = r.read_buffer_view();
     int32_t version = r.read_int();
-    int32_t err = kZOk;
     Stat stat;
     int64_t op_zxid = 0;
-    {
-      PathRef ref = ref_of(path);
-      Shard& sh = shard_of(ref);
-      std::unique_lock<std::mutex> lk = lock_shard(sh);
-      bump(cnt(c).tree_locks);
-      ZNode* n = sh.nodes.find(ref);
-      if (!n) {
-        err = kZNoNode;
-      } else if (version != -1 && version != n->stat.version) {
-        err = kZBadVersion;
-      } else {
-        int64_t zz = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
-        op_zxid = zz;
-        n->set_data(data);  // in place while it fits; the node never moves
-        n->stat.mzxid = zz;
-        n->stat.mtime = c->drain_wall_ms;
-        n->stat.version++;
-        n->stat.data_length = static_cast<int32_t>(data.size());
-        fire_data_watches_locked(sh, ref, kEventNodeDataChanged);
-        stat = n->stat;
-      }
-    }
-    if (err == kZOk)
-      send_stat_reply(c, xid, op_zxid, stat);
-    else
-      send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), err, nullptr);
+    int32_t err = with_node(c, path, [&](Shard& sh, const PathRef& ref, ZNode* n) {
+      if (!n) return kZNoNode;
+      if (version != -1 && version != n->stat.version) return kZBadVersion;
+      op_zxid = next_zxid();
+      apply_set_data(*n, data, op_zxid, c->drain_wall_ms);
+      fire_data_watches_locked(sh, ref, kEventNodeDataChanged);
+      stat = n->stat;
+      return kZOk;
+    });
+    if (err != kZOk) return send_error(c, xid, err);
+    send_stat_reply(c, xid, op_zxid, stat);
   }
 
-  void handle_get_children(Conn* c, int32_t xid, JuteReader& r) {
+  // getChildren, and getChildren2 (with_stat): the listing, then the node's Stat
+  void handle_get_children(Conn* c, int32_t xid, JuteReader& r, bool with_stat = false) {
     bump(cnt(c).get_children);
     std::string_view path = r.read_string_view();
     bool watch = r.read_bool();
-    int32_t err = kZOk;
-    GetChildrenResponse resp;
-    {
-      PathRef ref = ref_of(path);
-      Shard& sh = shard_of(ref);
-      std::unique_lock<std::mutex> lk = lock_shard(sh);
-      bump(cnt(c).tree_locks);
-      if (const ZNode* n = sh.nodes.find(ref)) {
-        if (watch) watch_set(sh.child_watches, ref).insert(sid_of(c));
-        list_children(*n, &resp.children);
-      } else {
-        err = kZNoNode;
-      }
-    }
-    if (err == kZOk)
-      send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), kZOk,
-                 [&](JuteWriter& w) { resp.serialize(w); });
-    else
-      send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), err, nullptr);
-  }
-
-  // getChildren2: children + the node's Stat (3.4+ clients use it by default)
-  void handle_get_children2(Conn* c, int32_t xid, JuteReader& r) {
-    bump(cnt(c).get_children);
-    std::string_view path = r.read_string_view();
-    bool watch = r.read_bool();
-    int32_t err = kZOk;
     GetChildrenResponse resp;
     Stat stat;
-    {
-      PathRef ref = ref_of(path);
-      Shard& sh = shard_of(ref);
-      std::unique_lock<std::mutex> lk = lock_shard(sh);
-      bump(cnt(c).tree_locks);
-      if (const ZNode* n = sh.nodes.find(ref)) {
-        if (watch) watch_set(sh.child_watches, ref).insert(sid_of(c));
-        list_children(*n, &resp.children);
-        stat = n->stat;
-      } else {
-        err = kZNoNode;
-      }
-    }
-    if (err == kZOk)
-      send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), kZOk, [&](JuteWriter& w) {
-        resp.serialize(w);
-        stat.serialize(w);
-      });
-    else
-      send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), err, nullptr);
+    int32_t err = with_node(c, path, [&](Shard& sh, const PathRef& ref, const ZNode* n) {
+      if (!n) return kZNoNode;
+      if (watch) watch_set(sh.child_watches, ref).insert(sid_of(c));
+      list_children(*n, &resp.children);
+      stat = n->stat;
+      return kZOk;
+    });
+    send_reply(c, xid, last_zxid(), err, [&](JuteWriter& w) {
+      resp.serialize(w);
+      if (with_stat) stat.serialize(w);
+    });
   }
 
   // multi (op 14): apply a create/delete/setData/check transaction
@@ -1499,19 +1141,17 @@ struct Ensemble::Impl {
           mo.version = req.version;
           break;
         }
-        case 13: {  // check(path, version)
+        case kOpCheck: {  // check(path, version)
           mo.path = r.read_string();
           mo.version = r.read_int();
           break;
         }
         default:
-          send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), kZMarshallingError, nullptr);
-          return;
+          return send_error(c, xid, kZMarshallingError);
       }
       mops.push_back(std::move(mo));
     }
 
-    int64_t sid = sid_of(c);
     std::vector<int32_t> results(mops.size(), kZOk);
     std::vector<std::string> created_paths(mops.size());
     // setData Stat snapshots taken while the shard locks are held — the
@@ -1623,7 +1263,7 @@ struct Ensemble::Impl {
               }
               break;
             }
-            case 13: {  // check
+            case kOpCheck: {
               if (!ov_exists(mo.path))
                 err = kZNoNode;
               else if (mo.version != -1 && mo.version != ov_version(mo.path))
@@ -1651,34 +1291,19 @@ struct Ensemble::Impl {
           switch (mo.type) {
             case kOpCreate: {
               bump(cnt(c).create);
-              int64_t zz = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
-              txn_zxid = zz;
+              txn_zxid = next_zxid();
               PathRef cref = ref_of(mo.path);
-              ZNode& n = *shard_of(cref).nodes.create(cref, mo.data);  // validated absent above
-              n.stat.czxid = zz;
-              n.stat.mzxid = zz;
-              n.stat.ctime = c->drain_wall_ms;
-              n.stat.mtime = n.stat.ctime;
-              n.stat.data_length = static_cast<int32_t>(mo.data.size());
-              if (mo.flags & kEphemeral) {
-                n.stat.ephemeral_owner = sid;
-                if (mine) {
-                  // same alive/link handshake as handle_create; a create
-                  // that loses it is rolled back once the locks are released
-                  std::lock_guard<std::mutex> eg(mine->eph_mu);
-                  bump(cnt(c).tree_locks);
-                  n.owner = mine.get();
-                  if (mine->alive.load(std::memory_order_relaxed))
-                    eph_link(*mine, n);
-                  else
-                    rollback.push_back(mo.path);
-                }
-              }
-              if (ZNode* par = find_node(ref_of(parent))) {
-                link_child(*par, n);
-                par->stat.cversion++;
-                par->stat.pzxid = zz;
-                par->stat.num_children = par->nchildren;
+              // validated above: the path is absent and the parent is there
+              ZNode& n = insert_node(shard_of(cref), cref, mo.data, *find_node(ref_of(parent)), txn_zxid,
+                                     c->drain_wall_ms);
+              if ((mo.flags & kEphemeral) && mine) {
+                // a create that finds its session dead is rolled back once
+                // the locks are released (own_ephemeral has the argument)
+                std::lock_guard<std::mutex> eg(mine->eph_mu);
+                bump(cnt(c).tree_locks);
+                bool alive = mine->alive.load(std::memory_order_relaxed);
+                own_ephemeral(n, *mine, alive);
+                if (!alive) rollback.push_back(mo.path);
               }
               data_events.push_back({mo.path, kEventNodeCreated});
               child_events.push_back(parent);
@@ -1687,19 +1312,14 @@ struct Ensemble::Impl {
             }
             case kOpDelete: {
               bump(cnt(c).del);
-              int64_t zz = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
-              txn_zxid = zz;
+              txn_zxid = next_zxid();
               PathRef cref = ref_of(mo.path);
               Shard& csh = shard_of(cref);
               if (ZNode* n = csh.nodes.find(cref)) {
                 // may be ANOTHER session's ephemeral: leaves its owner's index
-                bump(cnt(c).tree_locks, static_cast<uint64_t>(detach_ephemeral(*n)));
-                if (ZNode* par = n->parent) {
-                  unlink_child(*n);
-                  par->stat.cversion++;
-                  par->stat.pzxid = zz;
-                  par->stat.num_children = par->nchildren;
-                }
+                int took = 0;
+                detach_node(*n, txn_zxid, nullptr, &took);
+                bump(cnt(c).tree_locks, static_cast<uint64_t>(took));
                 csh.nodes.erase(n);
               }
               data_events.push_back({mo.path, kEventNodeDeleted});
@@ -1709,14 +1329,9 @@ struct Ensemble::Impl {
             }
             case kOpSetData: {
               bump(cnt(c).set_data);
-              int64_t zz = zxid_counter.fetch_add(1, std::memory_order_relaxed) + 1;
-              txn_zxid = zz;
+              txn_zxid = next_zxid();
               if (ZNode* n = find_node(ref_of(mo.path))) {
-                n->set_data(mo.data);
-                n->stat.mzxid = zz;
-                n->stat.mtime = c->drain_wall_ms;
-                n->stat.version++;
-                n->stat.data_length = static_cast<int32_t>(mo.data.size());
+                apply_set_data(*n, mo.data, txn_zxid, c->drain_wall_ms);
                 setdata_stats[i] = n->stat;
               }
               data_events.push_back({mo.path, kEventNodeDataChanged});
@@ -1751,7 +1366,7 @@ struct Ensemble::Impl {
 
     // reply with THIS txn's last zxid (not a fresh counter read, which may
     // already reflect other connections' later commits)
-    int64_t z = txn_zxid ? txn_zxid : zxid_counter.load(std::memory_order_relaxed);
+    int64_t z = txn_zxid ? txn_zxid : last_zxid();
     send_reply_with_body(c, xid, z, txn_err, [&](JuteWriter& w) {
       for (size_t i = 0; i < mops.size(); i++) {
         MultiHeader mh;
@@ -1783,114 +1398,65 @@ struct Ensemble::Impl {
     SetWatchesRequest req;
     req.deserialize(r);
     int64_t sid = sid_of(c);
-    for (const auto& path : req.data_watches) {
-      bool fire_changed = false, fire_deleted = false;
-      {
-        PathRef ref = ref_of(path);
-        Shard& sh = shard_of(ref);
-        std::unique_lock<std::mutex> lk = lock_shard(sh);
-        bump(cnt(c).tree_locks);
-        const ZNode* n = sh.nodes.find(ref);
-        if (!n)
-          fire_deleted = true;
-        else if (n->stat.mzxid > req.relative_zxid)
-          fire_changed = true;
-        else
-          watch_set(sh.data_watches, ref).insert(sid);
+    // `missed` names the event a node's state calls for, or kEventNone to arm
+    // the watch in `map`. The event goes out once the shard lock is released.
+    auto rearm = [&](const std::vector<std::string>& paths, WatchMap Shard::*map, auto missed) {
+      for (const auto& path : paths) {
+        int32_t ev = with_node(c, path, [&](Shard& sh, const PathRef& ref, const ZNode* n) {
+          int32_t e = missed(n);
+          if (e == kEventNone) watch_set(sh.*map, ref).insert(sid);
+          return e;
+        });
+        if (ev != kEventNone) deliver_watch({sid}, path, ev);
       }
-      if (fire_deleted) deliver_watch({sid}, path, kEventNodeDeleted);
-      if (fire_changed) deliver_watch({sid}, path, kEventNodeDataChanged);
-    }
-    for (const auto& path : req.exist_watches) {
-      bool fire_created = false;
-      {
-        PathRef ref = ref_of(path);
-        Shard& sh = shard_of(ref);
-        std::unique_lock<std::mutex> lk = lock_shard(sh);
-        bump(cnt(c).tree_locks);
-        if (sh.nodes.find(ref))
-          fire_created = true;  // appeared while the client was away
-        else
-          watch_set(sh.data_watches, ref).insert(sid);
-      }
-      if (fire_created) deliver_watch({sid}, path, kEventNodeCreated);
-    }
-    for (const auto& path : req.child_watches) {
-      bool fire_child = false, fire_deleted = false;
-      {
-        PathRef ref = ref_of(path);
-        Shard& sh = shard_of(ref);
-        std::unique_lock<std::mutex> lk = lock_shard(sh);
-        bump(cnt(c).tree_locks);
-        const ZNode* n = sh.nodes.find(ref);
-        if (!n)
-          fire_deleted = true;
-        else if (n->stat.pzxid > req.relative_zxid)
-          fire_child = true;
-        else
-          watch_set(sh.child_watches, ref).insert(sid);
-      }
-      if (fire_deleted) deliver_watch({sid}, path, kEventNodeDeleted);
-      if (fire_child) deliver_watch({sid}, path, kEventNodeChildrenChanged);
-    }
-    send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), kZOk, nullptr);
+    };
+    int64_t since = req.relative_zxid;
+    rearm(req.data_watches, &Shard::data_watches, [&](const ZNode* n) {
+      return !n ? kEventNodeDeleted : n->stat.mzxid > since ? kEventNodeDataChanged : kEventNone;
+    });
+    rearm(req.exist_watches, &Shard::data_watches, [](const ZNode* n) {
+      return n ? kEventNodeCreated : kEventNone;  // appeared while the client was away
+    });
+    rearm(req.child_watches, &Shard::child_watches, [&](const ZNode* n) {
+      return !n ? kEventNodeDeleted : n->stat.pzxid > since ? kEventNodeChildrenChanged : kEventNone;
+    });
+    send_ack(c, xid);
   }
 
   // sync: single-copy tree ⇒ always in sync; echo the path back
   void handle_sync(Conn* c, int32_t xid, JuteReader& r) {
     std::string path = r.read_string();
-    send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), kZOk,
-               [&](JuteWriter& w) { w.write_string(path); });
+    send_reply(c, xid, last_zxid(), kZOk, [&](JuteWriter& w) { w.write_string(path); });
   }
 
   // ACLs: everything is world:anyone (matching the reference's deployments);
   // getACL reports the open ACL, setACL acks without enforcement
   void handle_get_acl(Conn* c, int32_t xid, JuteReader& r) {
     std::string path = r.read_string();
-    int32_t err = kZOk;
     Stat stat;
-    {
-      PathRef ref = ref_of(path);
-      Shard& sh = shard_of(ref);
-      std::unique_lock<std::mutex> lk = lock_shard(sh);
-      bump(cnt(c).tree_locks);
-      if (const ZNode* n = sh.nodes.find(ref))
-        stat = n->stat;
-      else
-        err = kZNoNode;
-    }
-    if (err == kZOk)
-      send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), kZOk, [&](JuteWriter& w) {
-        write_acl_vector(w, {ACL{}});
-        stat.serialize(w);
-      });
-    else
-      send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), err, nullptr);
+    int32_t err = with_node(c, path, [&](Shard&, const PathRef&, const ZNode* n) {
+      if (!n) return kZNoNode;
+      stat = n->stat;
+      return kZOk;
+    });
+    send_reply(c, xid, last_zxid(), err, [&](JuteWriter& w) {
+      write_acl_vector(w, {ACL{}});
+      stat.serialize(w);
+    });
   }
 
   void handle_set_acl(Conn* c, int32_t xid, JuteReader& r) {
     std::string path = r.read_string();
     (void)read_acl_vector(r);
     r.read_int();  // version
-    int32_t err = kZOk;
     Stat stat;
-    {
-      PathRef ref = ref_of(path);
-      Shard& sh = shard_of(ref);
-      std::unique_lock<std::mutex> lk = lock_shard(sh);
-      bump(cnt(c).tree_locks);
-      if (ZNode* n = sh.nodes.find(ref)) {
-        n->stat.aversion++;
-        stat = n->stat;
-      } else {
-        err = kZNoNode;
-      }
-    }
-    if (err == kZOk)
-      send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), kZOk,
-                 [&](JuteWriter& w) { stat.serialize(w); });
-    else
-      send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), err, nullptr);
+    int32_t err = with_node(c, path, [&](Shard&, const PathRef&, ZNode* n) {
+      if (!n) return kZNoNode;
+      n->stat.aversion++;
+      stat = n->stat;
+      return kZOk;
+    });
+    send_reply(c, xid, last_zxid(), err, [&](JuteWriter& w) { stat.serialize(w); });
   }
 
   void handle_close_session(Conn* c, int32_t xid) {
@@ -1900,7 +1466,7 @@ struct Ensemble::Impl {
       std::lock_guard<std::mutex> og(c->out_mu);
       c->closing = true;  // close after the reply drains
     }
-    send_reply(c, xid, zxid_counter.load(std::memory_order_relaxed), kZOk, nullptr);
+    send_ack(c, xid);
     if (sid != 0) kill_session(sid, /*close_conn_too=*/false);
   }
 
@@ -2198,7 +1764,16 @@ struct Ensemble::Impl {
     if (!watchers.empty()) deliver_watch(watchers, ref.path, kEventNodeDeleted);
   }
 
+  // One event packet, built once; every live watcher gets a copy.
   void deliver_watch(const std::set<int64_t>& watchers, std::string_view path, int32_t event_type) {
+    std::string pkt;
+    build_packet(&pkt, kXidWatcherEvent, -1, kZOk, [&](JuteWriter& w) {
+      WatcherEvent ev;
+      ev.type = event_type;
+      ev.state = kStateSyncConnected;
+      ev.path = std::string(path);
+      ev.serialize(w);
+    });
     for (int64_t sid : watchers) {
       uint64_t cid = 0;
       {
@@ -2209,73 +1784,72 @@ struct Ensemble::Impl {
       }
       if (cid == 0) continue;
       ConnPtr cp = lookup(cid);
-      if (!cp) continue;
-      std::string pkt;
-      begin_packet(&pkt);
-      JuteWriter w(&pkt);
-      ReplyHeader hdr;
-      hdr.xid = kXidWatcherEvent;
-      hdr.zxid = -1;
-      hdr.err = 0;
-      hdr.serialize(w);
-      WatcherEvent ev;
-      ev.type = event_type;
-      ev.state = kStateSyncConnected;
-      ev.path = std::string(path);
-      ev.serialize(w);
-      frame_packet(&pkt);
-      send_packet(cp.get(), std::move(pkt));
+      if (cp) send_packet(cp.get(), pkt);
     }
   }
 
   // ---------------- response sending ----------------
 
-  template <typename BodyFn>
-  void send_reply(Conn* c, int32_t xid, int64_t zxid, int32_t err, BodyFn body) {
-    // fast path (handlers run on the owner loop inside a drain): serialize
-    // straight into the connection's staging buffer — no lock, no allocation,
-    // no timer; the flush that ends the drain moves it to outbuf once
-    if (c->draining && latency_ms.load(std::memory_order_relaxed) == 0) {
-      if (c->dead.load(std::memory_order_relaxed)) return;
-      if constexpr (std::is_same_v<BodyFn, std::nullptr_t>) {
-        // header-only reply (acks and every error): fixed 20 bytes
-        stage_fixed(c, xid, zxid, err, 0, [](RawWriter&) {});
-      } else {
-        // variable-size bodies (getData, listings, ACLs): the generic writer
-        // into a scratch string, then one append
-        std::string& pkt = c->scratch;
-        begin_packet(&pkt);
-        JuteWriter w(&pkt);
-        ReplyHeader hdr;
-        hdr.xid = xid;
-        hdr.zxid = zxid;
-        hdr.err = err;
-        hdr.serialize(w);
-        if (err == kZOk) body(w);
-        frame_packet(&pkt);
-        c->stage.append(pkt);
-        c->stage_pub.store(c->stage.size(), std::memory_order_release);
-      }
-      return;
-    }
-    std::string pkt;
-    begin_packet(&pkt);
-    JuteWriter w(&pkt);
+  // Every reply and every watch event starts with this header; the two
+  // functions below are the only encoders of it.
+  // (inlined always, as ReplyHeader::serialize is: out of line it costs the
+  // in-place path a call per reply)
+  template <typename W>
+  [[gnu::always_inline]] static inline void write_reply_header(W& w, int32_t xid, int64_t zxid, int32_t err) {
     ReplyHeader hdr;
     hdr.xid = xid;
     hdr.zxid = zxid;
     hdr.err = err;
     hdr.serialize(w);
-    if constexpr (!std::is_same_v<BodyFn, std::nullptr_t>) {
-      if (err == kZOk) body(w);
+  }
+
+  // A whole framed packet into *pkt (overwritten): length prefix, header,
+  // then whatever body writes.
+  template <typename BodyFn>
+  static void build_packet(std::string* pkt, int32_t xid, int64_t zxid, int32_t err, BodyFn body) {
+    begin_packet(pkt);
+    JuteWriter w(pkt);
+    write_reply_header(w, xid, zxid, err);
+    body(w);
+    frame_packet(pkt);
+  }
+
+  // true: replies are laid straight into the connection's staging buffer
+  // (handlers run on the owner loop inside a drain) — no lock, no allocation,
+  // no timer; the flush that ends the drain moves it to outbuf once
+  bool staging(const Conn* c) const { return c->draining && latency_ms.load(std::memory_order_relaxed) == 0; }
+
+  // A reply whose body (nullptr: none) goes out only when err is OK.
+  template <typename BodyFn>
+  void send_reply(Conn* c, int32_t xid, int64_t zxid, int32_t err, BodyFn body) {
+    constexpr bool kHasBody = !std::is_same_v<BodyFn, std::nullptr_t>;
+    auto body_if_ok = [&](JuteWriter& w) {
+      if constexpr (kHasBody) {
+        if (err == kZOk) body(w);
+      }
+    };
+    if (staging(c)) {
+      if (c->dead.load(std::memory_order_relaxed)) return;
+      if (!kHasBody || err != kZOk) {
+        // header-only reply (acks and every error): fixed 20 bytes
+        stage_fixed(c, xid, zxid, err, 0, [](RawWriter&) {});
+      } else {
+        // variable-size bodies (getData, listings, ACLs): the generic writer
+        // into a scratch string, then one append
+        build_packet(&c->scratch, xid, zxid, err, body_if_ok);
+        c->stage.append(c->scratch);
+        c->stage_pub.store(c->stage.size(), std::memory_order_release);
+      }
+      return;
     }
-    frame_packet(&pkt);
+    std::string pkt;
+    build_packet(&pkt, xid, zxid, err, body_if_ok);
     send_packet(c, std::move(pkt));
   }
 
-  void send_reply(Conn* c, int32_t xid, int64_t zxid, int32_t err, std::nullptr_t) {
-    send_reply<std::nullptr_t>(c, xid, zxid, err, nullptr);
-  }
+  // header-only replies at a fresh zxid read (nothing was committed)
+  void send_error(Conn* c, int32_t xid, int32_t err) { send_reply(c, xid, last_zxid(), err, nullptr); }
+  void send_ack(Conn* c, int32_t xid) { send_error(c, xid, kZOk); }
 
   // Owner loop, inside a drain, no latency injection: lay one reply of known
   // size down in the staging buffer. Room for the frame prefix, the
@@ -2287,11 +1861,7 @@ struct Ensemble::Impl {
     size_t n = ReplyHeader::kWireSize + (err == kZOk ? body_size : 0);
     RawWriter w(c->stage.reserve(4 + n));
     w.write_int(static_cast<int32_t>(n));
-    ReplyHeader hdr;
-    hdr.xid = xid;
-    hdr.zxid = zxid;
-    hdr.err = err;
-    hdr.serialize(w);
+    write_reply_header(w, xid, zxid, err);
     if (err == kZOk) body(w);
     c->stage.commit(4 + n);
     c->stage_pub.store(c->stage.size(), std::memory_order_release);
@@ -2303,7 +1873,7 @@ struct Ensemble::Impl {
   // sends from outside a drain), so the field order lives in one place.
   template <typename BodyFn>
   void send_fixed_reply(Conn* c, int32_t xid, int64_t zxid, size_t body_size, BodyFn body) {
-    if (c->draining && latency_ms.load(std::memory_order_relaxed) == 0) {
+    if (staging(c)) {
       if (c->dead.load(std::memory_order_relaxed)) return;
       stage_fixed(c, xid, zxid, kZOk, body_size, body);
       return;
@@ -2319,15 +1889,7 @@ struct Ensemble::Impl {
   template <typename BodyFn>
   void send_reply_with_body(Conn* c, int32_t xid, int64_t zxid, int32_t err, BodyFn body) {
     std::string pkt;
-    begin_packet(&pkt);
-    JuteWriter w(&pkt);
-    ReplyHeader hdr;
-    hdr.xid = xid;
-    hdr.zxid = zxid;
-    hdr.err = err;
-    hdr.serialize(w);
-    body(w);
-    frame_packet(&pkt);
+    build_packet(&pkt, xid, zxid, err, body);
     send_packet(c, std::move(pkt));
   }
 
@@ -2397,18 +1959,9 @@ struct Ensemble::Impl {
     }
     if (c->outbuf.empty()) {
       size_t off = 0;
-      while (off < pkt.size()) {
-        ssize_t n = send(c->fd, pkt.data() + off, pkt.size() - off, MSG_NOSIGNAL);
-        if (n > 0) {
-          off += static_cast<size_t>(n);
-        } else if (n < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) {
-          break;
-        } else if (n < 0 && errno == EINTR) {
-          continue;
-        } else {
-          mark_dead(c);
-          return;
-        }
+      if (send_some(c->fd, pkt.data(), pkt.size(), &off) == SendResult::kError) {
+        mark_dead(c);
+        return;
       }
       if (off < pkt.size()) {
         c->outbuf.append(pkt.data() + off, pkt.size() - off);  // outbuf is empty here
@@ -2470,19 +2023,7 @@ struct Ensemble::Impl {
         c->stage_pub.store(0, std::memory_order_relaxed);
       }
       size_t off = 0;
-      while (off < c->outbuf.size()) {
-        ssize_t n = send(c->fd, c->outbuf.data() + off, c->outbuf.size() - off, MSG_NOSIGNAL);
-        if (n > 0) {
-          off += static_cast<size_t>(n);
-        } else if (n < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) {
-          break;
-        } else if (n < 0 && errno == EINTR) {
-          continue;
-        } else {
-          close_now = true;
-          break;
-        }
-      }
+      close_now = send_some(c->fd, c->outbuf.data(), c->outbuf.size(), &off) == SendResult::kError;
       if (!close_now) {
         c->outbuf.erase_front(off);
         if (c->outbuf.empty()) {
@@ -2688,7 +2229,7 @@ std::vector<std::string> Ensemble::children(const std::string& path) const {
   PathRef ref = ref_of(path);
   auto& sh = impl_->shard_of(ref);
   std::lock_guard<std::mutex> g(sh.mu);
-  if (const auto* n = sh.nodes.find(ref)) Impl::list_children(*n, &out);
+  if (const auto* n = sh.nodes.find(ref)) list_children(*n, &out);
   return out;
 }
 
@@ -2761,9 +2302,9 @@ std::vector<std::string> Ensemble::audit() const { return impl_->audit(); }
 NodeStoreLayout Ensemble::node_store_layout() {
   NodeStoreLayout l;
   l.shards = Impl::kShards;
-  l.header_bytes = sizeof(Impl::ZNode);
-  l.max_cached_per_class = Impl::kMaxCachedPerClass;
-  l.classes.assign(std::begin(Impl::kBlockClasses), std::end(Impl::kBlockClasses));
+  l.header_bytes = sizeof(ZNode);
+  l.max_cached_per_class = kMaxCachedPerClass;
+  l.classes.assign(std::begin(kBlockClasses), std::end(kBlockClasses));
   return l;
 }
 

@@ -42,9 +42,11 @@ enum OpCode : int32_t {
   kOpSync = 9,
   kOpPing = 11,
   kOpGetChildren2 = 12,
+  kOpCheck = 13,  // only inside a multi
   kOpMulti = 14,
   kOpCreate2 = 15,
   kOpCloseSession = -11,
+  kOpAuth = 100,
   kOpSetWatches = 101,
   kOpError = -1,
 };
@@ -179,13 +181,14 @@ class RawWriter {
  public:
   explicit RawWriter(char* p) : p_(p) {}
 
-  void write_int(int32_t v) {
+  // a byte swap and one store each: always inlined, like JuteReader::read_int
+  [[gnu::always_inline]] inline void write_int(int32_t v) {
     uint32_t u = __builtin_bswap32(static_cast<uint32_t>(v));
     memcpy(p_, &u, 4);
     p_ += 4;
   }
 
-  void write_long(int64_t v) {
+  [[gnu::always_inline]] inline void write_long(int64_t v) {
     uint64_t u = __builtin_bswap64(static_cast<uint64_t>(v));
     memcpy(p_, &u, 8);
     p_ += 8;
@@ -419,8 +422,10 @@ struct ReplyHeader {
 
   static constexpr size_t kWireSize = 16;
 
+  // inlined always: every reply the server stages in place goes through it,
+  // and out of line it costs a call per reply
   template <typename W>
-  void serialize(W& w) const {
+  [[gnu::always_inline]] inline void serialize(W& w) const {
     w.write_int(xid);
     w.write_long(zxid);
     w.write_int(err);
