@@ -7,8 +7,9 @@
 // (which write disjoint domain subtrees) never contend:
 //
 //   - znodes + their watch maps live in 64 hash shards, each under its own
-//     mutex; an op locks only the shard(s) of the paths it touches (create/
-//     delete lock child+parent shards in index order),
+//     lock (a TreeLock, node_store.hpp); an op locks only the shard(s) of the
+//     paths it touches (create/delete lock child+parent shards in index
+//     order),
 //   - sessions live under one session mutex, but per-request touch is a
 //     lock-free atomic store through the connection's cached session pointer,
 //   - zxid is a global atomic counter,
@@ -96,7 +97,7 @@ struct Ensemble::Impl {
   using WatchMap = std::unordered_map<PathKey, std::set<int64_t>, PathHash, PathEq>;
 
   struct Shard {
-    std::mutex mu;
+    TreeLock mu;
     // threads waiting in lock_shard; a drain that carries mu reads it before
     // every request (acquire_for)
     std::atomic<uint32_t> waiters{0};
@@ -174,7 +175,9 @@ struct Ensemble::Impl {
   // eph_mu once per run, not once per request.
   //
   // Canonical lock order: shards by ascending index, then ONE eph_mu (two are
-  // never held at once), then session_mu → conns_mu → conn->out_mu.
+  // never held at once), then session_mu → conns_mu → conn->out_mu. The shard
+  // locks and eph_mu are TreeLocks (node_store.hpp: try_lock and unlock are
+  // one inline atomic each); the rest are std::mutex.
   // Blocking rule: a thread may BLOCK on a mutex only if everything it holds
   // comes earlier in that order. A carrying thread holds the parent's shard
   // and possibly eph_mu, so it takes a child shard with try_lock only; if
@@ -192,10 +195,10 @@ struct Ensemble::Impl {
   // no way out of the drain leaves a mutex locked. Everything that is not a
   // plain create/create2/delete releases first (handle_frame): any other op
   // may lock the carried shard itself (an exists on the parent's own shard
-  // would otherwise deadlock on a std::mutex this thread holds), and
+  // would otherwise deadlock on a TreeLock this thread holds), and
   // closeSession runs kill_session, which wants eph_mu with nothing held.
   struct Carry {
-    std::mutex* shard_mu = nullptr;  // the parent shard's mutex, locked
+    TreeLock* shard_mu = nullptr;  // the parent shard's lock, held
     size_t shard_idx = 0;
     Session* eph = nullptr;  // the session whose eph_mu is held
     uint32_t served = 0;     // requests served since shard_mu was taken
@@ -262,17 +265,17 @@ struct Ensemble::Impl {
 
   // Lock two shards without deadlock (index order; may be the same shard).
   struct TwoShardLock {
-    std::unique_lock<std::mutex> a, b;
+    std::unique_lock<TreeLock> a, b;
     Shard* first;   // shard i1
     Shard* second;  // shard i2
     TwoShardLock(Impl& impl, size_t i1, size_t i2) {
       first = &impl.shards[i1];
       second = &impl.shards[i2];
       if (i1 == i2) {
-        a = std::unique_lock<std::mutex>(impl.shards[i1].mu);
+        a = std::unique_lock<TreeLock>(impl.shards[i1].mu);
       } else {
-        a = std::unique_lock<std::mutex>(impl.shards[std::min(i1, i2)].mu);
-        b = std::unique_lock<std::mutex>(impl.shards[std::max(i1, i2)].mu);
+        a = std::unique_lock<TreeLock>(impl.shards[std::min(i1, i2)].mu);
+        b = std::unique_lock<TreeLock>(impl.shards[std::max(i1, i2)].mu);
       }
     }
     TwoShardLock(Impl& impl, const PathRef& p1, const PathRef& p2)
@@ -360,7 +363,7 @@ struct Ensemble::Impl {
       if (o == eph_held) {
         eph_unlink(*o, n);
       } else {
-        std::lock_guard<std::mutex> eg(o->eph_mu);
+        std::lock_guard<TreeLock> eg(o->eph_mu);
         eph_unlink(*o, n);
         ++*locks;
       }
@@ -404,15 +407,15 @@ struct Ensemble::Impl {
   // request, or taken now. The child's shard (cidx) is returned as a lock of
   // the caller's scope, empty when the child lives in the parent's shard.
   // While k holds anything the child is only tried; see Carry for the rule.
-  std::unique_lock<std::mutex> acquire_for(Carry& k, size_t cidx, size_t pidx, int* locks) {
+  std::unique_lock<TreeLock> acquire_for(Carry& k, size_t cidx, size_t pidx, int* locks) {
     // the carry ends at its bound, at a parent in another shard, and as soon
     // as anybody is seen waiting for the carried shard (lock_shard)
     if (k.shard_mu && (k.shard_idx != pidx || k.served >= kCarryBound ||
                        shards[k.shard_idx].waiters.load(std::memory_order_relaxed) != 0))
       k.release();
-    std::unique_lock<std::mutex> child;
+    std::unique_lock<TreeLock> child;
     if (k.shard_mu && cidx != pidx) {
-      child = std::unique_lock<std::mutex>(shards[cidx].mu, std::try_to_lock);
+      child = std::unique_lock<TreeLock>(shards[cidx].mu, std::try_to_lock);
       if (child.owns_lock())
         ++*locks;
       else
@@ -444,8 +447,8 @@ struct Ensemble::Impl {
   // at that count before each request and lets go at once. That takes it
   // about one request, so spinning for a moment first is cheaper than going
   // to sleep in the kernel and being woken.
-  static std::unique_lock<std::mutex> lock_shard(Shard& sh) {
-    std::unique_lock<std::mutex> lk(sh.mu, std::try_to_lock);
+  static std::unique_lock<TreeLock> lock_shard(Shard& sh) {
+    std::unique_lock<TreeLock> lk(sh.mu, std::try_to_lock);
     if (lk.owns_lock()) return lk;
     sh.waiters.fetch_add(1, std::memory_order_relaxed);
     for (int i = 0; i < 512 && !lk.owns_lock(); i++) {
@@ -464,7 +467,7 @@ struct Ensemble::Impl {
   auto with_node(Conn* c, std::string_view path, Fn fn) {
     PathRef ref = ref_of(path);
     Shard& sh = shard_of(ref);
-    std::unique_lock<std::mutex> lk = lock_shard(sh);
+    std::unique_lock<TreeLock> lk = lock_shard(sh);
     bump(cnt(c).tree_locks);
     return fn(sh, ref, sh.nodes.find(ref));
   }
@@ -890,19 +893,20 @@ struct Ensemble::Impl {
     std::string seq_path;  // SEQUENCE only: the path with its suffix
     std::string_view final_path = path;
     int locks = 0;  // mutexes this request took (tree_locks)
-    if (!valid_path(path) || path == "/") {
+    size_t last_slash = 0;  // one pass validates the path and finds its parent
+    if (!scan_path(path, &last_slash) || path.size() == 1) {  // "/" is the one valid path of a byte
       err = kZMarshallingError;
     } else {
       // one hash per path: it picks the shard and probes the map
       PathRef cref = ref_of(path);
-      PathRef pref = parent_ref(c, parent_view(path));
+      PathRef pref = parent_ref(c, parent_of(path, last_slash));
       // A SEQUENCE create carries nothing: it lets go of the drain's locks
       // and runs under a carry of its own, which this scope releases.
       Carry own_locks;
       if (flags & kSequence) c->carry->release();
       Carry& k = (flags & kSequence) ? own_locks : *c->carry;
       Shard* first_csh = &shard_of(cref);
-      std::unique_lock<std::mutex> child_lk = acquire_for(k, cref.hash % kShards, pref.hash % kShards, &locks);
+      std::unique_lock<TreeLock> child_lk = acquire_for(k, cref.hash % kShards, pref.hash % kShards, &locks);
       Shard& psh = shard_of(pref);
       ZNode* parp = psh.nodes.find(pref);
       if (!parp) {
@@ -912,7 +916,7 @@ struct Ensemble::Impl {
       } else {
         ZNode& par = *parp;
         Shard* csh = first_csh;
-        std::unique_lock<std::mutex> extra;
+        std::unique_lock<TreeLock> extra;
         if (flags & kSequence) {
           char suffix[16];
           snprintf(suffix, sizeof(suffix), "%010d", par.stat.cversion);
@@ -926,7 +930,7 @@ struct Ensemble::Impl {
           // corner
           csh = &shard_of(cref);
           if (csh != first_csh && csh != &psh) {
-            extra = std::unique_lock<std::mutex>(csh->mu, std::try_to_lock);
+            extra = std::unique_lock<TreeLock>(csh->mu, std::try_to_lock);
             if (!extra.owns_lock())
               err = kZSystemError;  // pathological shard collision
             else
@@ -979,7 +983,7 @@ struct Ensemble::Impl {
       PathRef cref = ref_of(path);
       PathRef pref = parent_ref(c, parent_view(path));
       Carry& k = *c->carry;
-      std::unique_lock<std::mutex> child_lk = acquire_for(k, cref.hash % kShards, pref.hash % kShards, &locks);
+      std::unique_lock<TreeLock> child_lk = acquire_for(k, cref.hash % kShards, pref.hash % kShards, &locks);
       Shard& csh = shard_of(cref);
       ZNode* n = csh.nodes.find(cref);
       if (!n || path == "/") {
@@ -1175,7 +1179,7 @@ struct Ensemble::Impl {
         idxs.insert(ref_of(mo.path).hash % kShards);
         idxs.insert(ref_of(parent_view(mo.path)).hash % kShards);
       }
-      std::vector<std::unique_lock<std::mutex>> locks;
+      std::vector<std::unique_lock<TreeLock>> locks;
       locks.reserve(idxs.size());
       for (size_t i : idxs) locks.emplace_back(shards[i].mu);
       bump(cnt(c).tree_locks, locks.size());
@@ -1299,7 +1303,7 @@ struct Ensemble::Impl {
               if ((mo.flags & kEphemeral) && mine) {
                 // a create that finds its session dead is rolled back once
                 // the locks are released (own_ephemeral has the argument)
-                std::lock_guard<std::mutex> eg(mine->eph_mu);
+                std::lock_guard<TreeLock> eg(mine->eph_mu);
                 bump(cnt(c).tree_locks);
                 bool alive = mine->alive.load(std::memory_order_relaxed);
                 own_ephemeral(n, *mine, alive);
@@ -1497,7 +1501,7 @@ struct Ensemble::Impl {
       // inside its own eph_mu section, so everything ever linked is linked
       // before this store and is found by the drain below (handle_create
       // has the full argument)
-      std::lock_guard<std::mutex> eg(s->eph_mu);
+      std::lock_guard<TreeLock> eg(s->eph_mu);
       s->alive.store(false, std::memory_order_release);
     }
     // Drain one node at a time: pop it under eph_mu (a linked node cannot be
@@ -1513,7 +1517,7 @@ struct Ensemble::Impl {
     std::string p;
     while (true) {
       {
-        std::lock_guard<std::mutex> eg(s->eph_mu);
+        std::lock_guard<TreeLock> eg(s->eph_mu);
         ZNode* n = s->eph_head;
         if (!n) break;
         p.assign(n->path());
@@ -1566,7 +1570,7 @@ struct Ensemble::Impl {
     auto bad = [&out](std::string_view where, const std::string& what) {
       out.push_back(std::string(where) + ": " + what);
     };
-    std::vector<std::unique_lock<std::mutex>> locks;
+    std::vector<std::unique_lock<TreeLock>> locks;
     locks.reserve(kShards);
     for (auto& sh : shards) locks.emplace_back(sh.mu);
     std::vector<SessionPtr> snap;
@@ -1578,7 +1582,7 @@ struct Ensemble::Impl {
       }
     }
     std::sort(snap.begin(), snap.end(), [](const SessionPtr& a, const SessionPtr& b) { return a->id < b->id; });
-    std::vector<std::unique_lock<std::mutex>> eph_locks;
+    std::vector<std::unique_lock<TreeLock>> eph_locks;
     eph_locks.reserve(snap.size());
     std::unordered_set<const Session*> known;
     for (const auto& s : snap) {
@@ -1654,7 +1658,7 @@ struct Ensemble::Impl {
             if (known.count(owner)) {
               linked = n->eph_linked;  // its eph_mu is held
             } else {
-              std::lock_guard<std::mutex> eg(owner->eph_mu);
+              std::lock_guard<TreeLock> eg(owner->eph_mu);
               linked = n->eph_linked;
             }
           }
@@ -2214,7 +2218,7 @@ void Ensemble::set_latency_ms(int ms) { impl_->latency_ms.store(ms); }
 NodeInfo Ensemble::get(const std::string& path) const {
   PathRef ref = ref_of(path);
   auto& sh = impl_->shard_of(ref);
-  std::lock_guard<std::mutex> g(sh.mu);
+  std::lock_guard<TreeLock> g(sh.mu);
   NodeInfo info;
   if (const auto* n = sh.nodes.find(ref)) {
     info.exists = true;
@@ -2228,7 +2232,7 @@ std::vector<std::string> Ensemble::children(const std::string& path) const {
   std::vector<std::string> out;
   PathRef ref = ref_of(path);
   auto& sh = impl_->shard_of(ref);
-  std::lock_guard<std::mutex> g(sh.mu);
+  std::lock_guard<TreeLock> g(sh.mu);
   if (const auto* n = sh.nodes.find(ref)) list_children(*n, &out);
   return out;
 }
@@ -2236,7 +2240,7 @@ std::vector<std::string> Ensemble::children(const std::string& path) const {
 size_t Ensemble::node_count() const {
   size_t n = 0;
   for (auto& sh : impl_->shards) {
-    std::lock_guard<std::mutex> g(sh.mu);
+    std::lock_guard<TreeLock> g(sh.mu);
     n += sh.nodes.size();
   }
   return n - 1;  // exclude root
@@ -2250,7 +2254,7 @@ size_t Ensemble::ephemeral_count() const {
   }
   size_t n = 0;
   for (const auto& s : snap) {
-    std::lock_guard<std::mutex> eg(s->eph_mu);
+    std::lock_guard<TreeLock> eg(s->eph_mu);
     n += s->eph_count;
   }
   return n;
@@ -2290,7 +2294,7 @@ std::map<std::string, uint64_t> Ensemble::counters() const {
   }
   uint64_t cached = 0;
   for (auto& sh : impl_->shards) {
-    std::lock_guard<std::mutex> g(sh.mu);
+    std::lock_guard<TreeLock> g(sh.mu);
     cached += sh.nodes.cached;
   }
   out["node_blocks_cached"] = cached;

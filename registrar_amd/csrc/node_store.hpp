@@ -3,10 +3,15 @@
 // pointer links between nodes (children of a parent, ephemerals of a session).
 //
 // Nothing in this header takes a lock or starts a thread. Every structure
-// here is guarded by a mutex its user holds; which one is stated at each
+// here is guarded by a lock its user holds; which one is stated at each
 // field. ensemble.cpp is that user (its Shard owns a NodeStore and the shard
-// mutex; Session::eph_mu is declared here next to the list it guards).
+// lock; Session::eph_mu is declared here next to the list it guards). The
+// type of those two locks, TreeLock, is defined here as well.
 #pragma once
+
+#include <linux/futex.h>
+#include <sys/syscall.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
@@ -25,18 +30,95 @@ namespace registrar {
 namespace zk {
 namespace detail {
 
-// Parent of a path as a view of the same bytes ("/" for depth-1 paths).
+// The lock of a shard (Shard::mu) and of a session's ephemeral list
+// (Session::eph_mu): the two a request handler takes, thousands of times per
+// drain and nearly always uncontended. It is the classic three-state futex
+// mutex. One word: 0 free, 1 held, 2 held and somebody may be asleep on it.
+// try_lock is one acquire compare-and-swap and unlock one release exchange,
+// both inline; only a lock() that finds the word taken leaves the line, and
+// only an unlock() that finds 2 enters the kernel.
+// No wake-up is lost: a thread sleeps only after it has itself written 2, and
+// FUTEX_WAIT returns at once unless the word still is 2; the unlock that
+// follows reads that 2 in its exchange and wakes one sleeper. A woken thread
+// takes the lock as 2 again, since others may still be asleep.
+// BasicLockable and Lockable, so std::lock_guard and std::unique_lock work.
+// Not recursive, no timed waits. Every other mutex here stays std::mutex.
+class TreeLock {
+ public:
+  TreeLock() = default;
+  TreeLock(const TreeLock&) = delete;
+  TreeLock& operator=(const TreeLock&) = delete;
+
+  bool try_lock() noexcept {
+    uint32_t expect = kFree;
+    return word_.compare_exchange_strong(expect, kHeld, std::memory_order_acquire, std::memory_order_relaxed);
+  }
+  void lock() noexcept {
+    if (!try_lock()) lock_slow();
+  }
+  void unlock() noexcept {
+    if (word_.exchange(kFree, std::memory_order_release) == kSleepers) wake_one();
+  }
+
+ private:
+  static constexpr uint32_t kFree = 0, kHeld = 1, kSleepers = 2;
+  static_assert(std::atomic<uint32_t>::is_always_lock_free && sizeof(std::atomic<uint32_t>) == sizeof(uint32_t),
+                "the futex word is the atomic itself");
+
+  long futex(int op, uint32_t val) noexcept {
+    return syscall(SYS_futex, reinterpret_cast<uint32_t*>(&word_), op, val, nullptr, nullptr, 0);
+  }
+  __attribute__((noinline, cold)) void lock_slow() noexcept {
+    // a holder keeps the lock for a request or a short run of them: look
+    // again a few times before paying for a sleep and a wake-up
+    for (int i = 0; i < 64; i++) {
+#if defined(__x86_64__) || defined(__i386__)
+      __builtin_ia32_pause();
+#endif
+      if (word_.load(std::memory_order_relaxed) == kFree && try_lock()) return;
+    }
+    while (word_.exchange(kSleepers, std::memory_order_acquire) != kFree) futex(FUTEX_WAIT_PRIVATE, kSleepers);
+  }
+  __attribute__((noinline, cold)) void wake_one() noexcept { futex(FUTEX_WAKE_PRIVATE, 1); }
+
+  std::atomic<uint32_t> word_{kFree};
+};
+
+// Parent of a path as a view of the same bytes ("/" for depth-1 paths). The
+// basename is short, so the last '/' is found by walking back from the end.
 inline std::string_view parent_view(std::string_view p) {
-  size_t pos = p.rfind('/');
-  if (pos == std::string_view::npos || pos == 0) return "/";
-  return p.substr(0, pos);
+  size_t pos = p.size();
+  while (pos > 0 && p[pos - 1] != '/') pos--;
+  if (pos <= 1) return "/";  // no '/' at all, or only the leading one
+  return p.substr(0, pos - 1);
+}
+
+// One pass over a path: true when it is not empty, starts with '/', does not
+// end in '/' unless it is "/" itself, and holds no "//". *last_slash is then
+// the index of its last '/', which is all parent_of needs.
+inline bool scan_path(std::string_view p, size_t* last_slash) {
+  const size_t n = p.size();
+  if (n == 0 || p[0] != '/') return false;
+  size_t last = 0;
+  for (size_t i = 1; i < n; i++) {
+    if (p[i] == '/') {
+      if (last + 1 == i) return false;
+      last = i;
+    }
+  }
+  if (n > 1 && last + 1 == n) return false;
+  *last_slash = last;
+  return true;
 }
 
 inline bool valid_path(std::string_view p) {
-  if (p.empty() || p[0] != '/') return false;
-  if (p.size() > 1 && p.back() == '/') return false;
-  if (p.find("//") != std::string_view::npos) return false;
-  return true;
+  size_t last_slash;
+  return scan_path(p, &last_slash);
+}
+
+// parent_view of a path scan_path accepted, from the index it reported
+inline std::string_view parent_of(std::string_view p, size_t last_slash) {
+  return p.substr(0, last_slash ? last_slash : 1);
 }
 
 // The node table and the watch maps are keyed by (path, hash of path). A
@@ -164,7 +246,7 @@ static_assert(sizeof(ZNode) < kBlockClasses[0], "smallest class must hold a head
 // One shard's nodes: an intrusive chained hash table (power-of-two bucket
 // array of ZNode*, the chain link and the full hash live in the node) plus
 // the shard's free lists of released blocks. Everything here is guarded by
-// the shard's mutex. Growth relinks nodes and never moves them.
+// the shard's lock. Growth relinks nodes and never moves them.
 struct NodeStore {
   ZNode** buckets = nullptr;
   size_t nbuckets = 0;  // power of two
@@ -322,7 +404,7 @@ struct Session {
   // false once kill_session starts; written under eph_mu, so a create that
   // reads it under eph_mu either links before the kill's drain or not at all
   std::atomic<bool> alive{true};
-  std::mutex eph_mu;
+  TreeLock eph_mu;
   // this session's ephemerals: intrusive list through ZNode::eph_prev/next
   // (no per-create allocation, no second copy of the path)
   ZNode* eph_head = nullptr;

@@ -14,7 +14,9 @@
 //     goes on expiring sessions. A register or heartbeat that loses to its
 //     peer there is expected and not counted,
 //   - then a crossed-parents phase on a two-loop ensemble of its own (see
-//     crossed_phase): the locks a drain carries, under contention.
+//     crossed_phase): the locks a drain carries, under contention,
+//   - then the tree's lock type on its own (see treelock_phase): eight
+//     threads, one TreeLock, one plain counter.
 // At the end, with every client closed and every session gone, the tree must
 // pass Ensemble::audit() and hold no ephemeral.
 // Exit code 0 = every cycle behaved and the end state is sound; sanitizers
@@ -33,6 +35,7 @@
 #include <vector>
 
 #include "ensemble.hpp"
+#include "node_store.hpp"
 #include "registrar.hpp"
 #include "zkclient.hpp"
 
@@ -189,6 +192,47 @@ bool crossed_phase(int seconds, const Logger& log) {
   cl[1]->close();
   ens.stop();
   return ok;
+}
+
+// TreeLock on its own: eight threads add to a PLAIN counter under one lock,
+// so a lost update (or, under the thread sanitizer, a missing acquire/release
+// edge) shows. Most sections are a bare increment, which keeps the word
+// contended and the spin path busy; every 512th holds the lock across a short
+// sleep, so the others run out of spins, mark sleepers and wait in the kernel
+// until the unlock wakes them. try_lock takes part too. Returns true when the
+// count is exact.
+bool treelock_phase() {
+  constexpr int kThreads = 8;
+  constexpr uint64_t kPerThread = 20000;
+  zk::detail::TreeLock mu;
+  uint64_t counter = 0;  // guarded by mu, deliberately not atomic
+  std::atomic<uint64_t> tried{0};
+  std::vector<std::thread> threads;
+  for (int t = 0; t < kThreads; t++) {
+    threads.emplace_back([&, t] {
+      for (uint64_t i = 0; i < kPerThread; i++) {
+        if ((i + static_cast<uint64_t>(t)) % 7 == 0) {
+          // the handlers' own pattern: try first, block only when taken
+          if (mu.try_lock())
+            tried.fetch_add(1, std::memory_order_relaxed);
+          else
+            mu.lock();
+          counter++;
+          mu.unlock();
+        } else {
+          std::lock_guard<zk::detail::TreeLock> g(mu);
+          counter++;
+          if (i % 512 == static_cast<uint64_t>(t)) std::this_thread::sleep_for(std::chrono::microseconds(200));
+        }
+      }
+    });
+  }
+  for (auto& th : threads) th.join();
+  bool held = !mu.try_lock();  // must be free at the end
+  if (!held) mu.unlock();
+  printf("stress: tree lock phase: count %llu of %llu, %llu by try_lock\n", static_cast<unsigned long long>(counter),
+         static_cast<unsigned long long>(kThreads * kPerThread), static_cast<unsigned long long>(tried.load()));
+  return !held && counter == kThreads * kPerThread;
 }
 }  // namespace
 
@@ -350,6 +394,7 @@ int main(int argc, char** argv) {
 
   // crossed parents (carried locks under contention), on its own ensemble
   bool crossed_ok = crossed_secs <= 0 || crossed_phase(crossed_secs, log);
+  bool treelock_ok = treelock_phase();
 
   // End state. Every client is closed, so every session ends: by its close,
   // or (where the close was lost to a killed server) by the expiry sweep. A
@@ -394,5 +439,6 @@ int main(int argc, char** argv) {
   // chaos timing, fail on systematic breakage
   bool behaved = cycles.load() > 0 && failures.load() < cycles.load() / 4 + 16;
   if (!crossed_ok) printf("stress: the crossed-parents phase failed\n");
-  return (behaved && sound && crossed_ok) ? 0 : 1;
+  if (!treelock_ok) printf("stress: the tree lock phase failed\n");
+  return (behaved && sound && crossed_ok && treelock_ok) ? 0 : 1;
 }
