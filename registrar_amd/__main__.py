@@ -3,7 +3,9 @@
 Subcommands:
   daemon   -f CONFIG [-v] [--exit-on-expiry]   run a registrar (same contract
                                                as the registrard binary)
-  ensemble [-n N] [-p PORT ...]                run a synthetic ZK ensemble
+  ensemble [-n N] [-p PORT ...] [--quorum]     run a synthetic ZK ensemble
+                                               (--quorum: no service below a
+                                               majority of servers)
   tree     --servers HOST:PORT[,...] [PATH]    dump a ZK subtree (Binder-style
                                                reader; works against the
                                                synthetic ensemble or real ZK)
@@ -61,7 +63,8 @@ def cmd_daemon(args):
 def cmd_ensemble(args):
     import registrar_amd as ra
 
-    ens = ra.Ensemble(servers=args.n, ports=args.port or [], log_level="info" if args.verbose else "warn")
+    ens = ra.Ensemble(servers=args.n, ports=args.port or [], log_level="info" if args.verbose else "warn",
+                      quorum=args.quorum)
     ens.start()
     print(json.dumps({"ports": ens.ports(), "connect": ens.connect_string()}), flush=True)
     stop = []
@@ -225,6 +228,8 @@ def main(argv=None):
     e.add_argument("-n", type=int, default=1)
     e.add_argument("-p", "--port", type=int, action="append")
     e.add_argument("-v", "--verbose", action="store_true")
+    e.add_argument("--quorum", action="store_true",
+                   help="no service and no session expiry below a majority of servers")
     e.set_defaults(fn=cmd_ensemble)
 
     t = sub.add_parser("tree", help="dump a ZK subtree")

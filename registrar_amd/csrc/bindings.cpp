@@ -132,7 +132,8 @@ PYBIND11_MODULE(_core, m) {
   py::class_<zk::Ensemble>(m, "Ensemble")
       .def(py::init([](size_t servers, int tick_ms, int min_session_timeout_ms, int max_session_timeout_ms,
                        int latency_ms, int election_ms, const std::string& log_level,
-                       const std::vector<int>& ports, const std::string& bind_host, int io_threads) {
+                       const std::vector<int>& ports, const std::string& bind_host, int io_threads,
+                       bool quorum) {
              zk::EnsembleConfig cfg;
              if (!ports.empty()) {
                cfg.ports = ports;
@@ -141,6 +142,7 @@ PYBIND11_MODULE(_core, m) {
              }
              cfg.bind_host = bind_host;
              cfg.io_threads = io_threads;
+             cfg.quorum = quorum;
              cfg.tick_ms = tick_ms;
              cfg.min_session_timeout_ms = min_session_timeout_ms;
              cfg.max_session_timeout_ms = max_session_timeout_ms;
@@ -152,7 +154,7 @@ PYBIND11_MODULE(_core, m) {
            py::arg("servers") = 1, py::arg("tick_ms") = 100, py::arg("min_session_timeout_ms") = 400,
            py::arg("max_session_timeout_ms") = 60000, py::arg("latency_ms") = 0, py::arg("election_ms") = 0,
            py::arg("log_level") = "warn", py::arg("ports") = std::vector<int>{},
-           py::arg("bind_host") = "127.0.0.1", py::arg("io_threads") = 0)
+           py::arg("bind_host") = "127.0.0.1", py::arg("io_threads") = 0, py::arg("quorum") = false)
       .def("start", &zk::Ensemble::start, py::call_guard<py::gil_scoped_release>())
       .def("stop", &zk::Ensemble::stop, py::call_guard<py::gil_scoped_release>())
       .def("ports", &zk::Ensemble::ports)
@@ -180,6 +182,23 @@ PYBIND11_MODULE(_core, m) {
       .def("zxid", &zk::Ensemble::zxid)
       .def("counters", &zk::Ensemble::counters)
       .def("audit", &zk::Ensemble::audit, py::call_guard<py::gil_scoped_release>())
+      .def("has_quorum", &zk::Ensemble::has_quorum)
+      .def("quorum_state",
+           [](const zk::Ensemble& e) {
+             zk::QuorumState q = e.quorum_state();
+             py::dict d;
+             d["enabled"] = q.enabled;
+             d["servers"] = q.servers;
+             d["servers_up"] = q.servers_up;
+             d["needed"] = q.needed;
+             d["has_quorum"] = q.has_quorum;
+             d["serving"] = q.serving;
+             d["leader"] = q.leader;
+             d["losses"] = q.losses;
+             d["refused_connects"] = q.refused_connects;
+             d["dropped_connections"] = q.dropped_connections;
+             return d;
+           })
       .def_static("node_store_layout", [] {
         zk::NodeStoreLayout l = zk::Ensemble::node_store_layout();
         py::dict d;

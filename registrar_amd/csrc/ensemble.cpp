@@ -22,6 +22,24 @@
 // parent shard and eph_mu across sibling requests takes child shards with
 // try_lock (struct Carry). kill_session drains the ephemeral set with no
 // other lock held before taking shard locks (see the phase comments).
+//
+// admin_mu (servers, leader, election, quorum state) stands outside that
+// chain: a thread takes it while holding none of the locks above. Under it a
+// thread may take session_mu (resume_serving restarts every session's timer),
+// and nothing else. Order: admin_mu → session_mu.
+//
+// Quorum mode (EnsembleConfig::quorum). The ensemble has quorum while more
+// than half of its servers are up; it serves while it has quorum, a leader,
+// and no election pause. Service is withheld at the door only, never per
+// request: `not_serving` (one atomic, written under admin_mu) is read by
+// accept, by the handshake and by the expiry sweep, and the call that stops
+// service closes every connection before it returns (kill_server: a barrier
+// through every IO loop, so that no accept, drain or sweep that began while
+// serving is still running, then a close of each connection on its own loop).
+// From then on no request handler runs, so the tree and zxid stand still
+// until resume_serving, which elects the lowest up index, sets every live
+// session's last_touch to now and only then clears `not_serving`. With the
+// mode off `not_serving` is never set and none of this runs.
 #include "ensemble.hpp"
 
 #include "node_store.hpp"
@@ -252,6 +270,12 @@ struct Ensemble::Impl {
   std::vector<Server> servers;
   size_t leader_idx = 0;
   int64_t election_until = 0;  // monotonic ms; connects refused until then
+  // quorum mode only (see the header comment). Written under admin_mu.
+  std::atomic<bool> not_serving{false};
+  bool has_leader = true;  // false from a quorum or leader loss until resume_serving
+  uint64_t quorum_losses = 0;
+  uint64_t dropped_conns = 0;
+  std::atomic<uint64_t> refused_connects{0};
 
   explicit Impl(EnsembleConfig c) : cfg(std::move(c)), log(Logger("zk-ensemble").child("ensemble")) {
     log.set_level(cfg.log_level);
@@ -504,6 +528,12 @@ struct Ensemble::Impl {
       std::lock_guard<std::mutex> g(admin_mu);
       servers.resize(n);
       for (size_t i = 0; i < n; i++) open_listener(i, cfg.ports[i]);
+      if (cfg.quorum) {  // every server is up: server 0 leads, no pause
+        leader_idx = 0;
+        has_leader = true;
+        election_until = 0;
+        not_serving.store(false, std::memory_order_relaxed);
+      }
     }
     for (size_t i = 0; i < io; i++) {
       threads.emplace_back([this, i] {
@@ -593,12 +623,15 @@ struct Ensemble::Impl {
       if (fd < 0) break;
       {
         std::lock_guard<std::mutex> g(admin_mu);
-        if (now_ms() < election_until) {
-          // mid-election: nobody serves (BASELINE config 4 storm realism)
+        if (now_ms() < election_until || not_serving.load(std::memory_order_relaxed)) {
+          // mid-election, or (quorum mode) below a majority: nobody serves
+          // (BASELINE config 4 storm realism)
           ::close(fd);
+          refused_connects.fetch_add(1, std::memory_order_relaxed);
           continue;
         }
-        maybe_elect_leader_locked();
+        // quorum mode chooses its leader when service resumes (resume_serving)
+        if (!cfg.quorum) maybe_elect_leader_locked();
       }
       set_nodelay(fd);
       auto conn = std::make_shared<Conn>();
@@ -716,10 +749,7 @@ struct Ensemble::Impl {
   bool handle_frame(Conn* c, const char* body, size_t len) {
     try {
       JuteReader r(body, len);
-      if (!c->handshaken) {
-        handle_connect(c, r);
-        return true;
-      }
+      if (!c->handshaken) return handle_connect(c, r);
       RequestHeader hdr;
       hdr.deserialize(r);
       touch(c);
@@ -794,7 +824,13 @@ struct Ensemble::Impl {
     }
   }
 
-  void handle_connect(Conn* c, JuteReader& r) {
+  // returns false ⇒ caller closes the conn with no ConnectResponse sent
+  bool handle_connect(Conn* c, JuteReader& r) {
+    if (not_serving.load(std::memory_order_relaxed)) {
+      // quorum mode: accepted while serving, but service stopped since
+      refused_connects.fetch_add(1, std::memory_order_relaxed);
+      return false;
+    }
     ConnectRequest req;
     req.deserialize(r);
     bump(cnt(c).connect);
@@ -867,6 +903,7 @@ struct Ensemble::Impl {
       c->closing = true;  // expired handshake: notify, then close
     }
     send_packet(c, std::move(pkt));
+    return true;
   }
 
   int64_t sid_of(Conn* c) const { return c->session ? c->session->id : 0; }
@@ -1539,7 +1576,9 @@ struct Ensemble::Impl {
   void schedule_sweep() {
     loops[0]->schedule(cfg.tick_ms, [this] {
       std::vector<int64_t> expired;
-      {
+      // quorum mode: only a leader expires sessions, and resume_serving has
+      // restarted every timer before this reads false again
+      if (!not_serving.load(std::memory_order_acquire)) {
         std::lock_guard<std::mutex> g(session_mu);
         int64_t now = now_ms();
         for (const auto& kv : sessions)
@@ -2078,7 +2117,97 @@ struct Ensemble::Impl {
     });
   }
 
-  // ---------------- control (any thread) ----------------
+  // ---------------- quorum mode (see the header comment) ----------------
+
+  enum class Stop { kNone, kQuorumLost, kLeaderLost };
+
+  // admin_mu held
+  size_t servers_up_locked() const {
+    size_t up = 0;
+    for (const auto& s : servers) up += s.up ? 1 : 0;
+    return up;
+  }
+
+  // admin_mu held; quorum mode; server idx has just gone from up to down.
+  // Says whether that ends service, and if so marks it ended.
+  Stop server_went_down_locked(size_t idx) {
+    size_t n = servers.size();
+    size_t up = servers_up_locked();
+    bool had = 2 * (up + 1) > n;
+    bool has = 2 * up > n;
+    if (had && !has) {
+      not_serving.store(true, std::memory_order_release);
+      has_leader = false;
+      quorum_losses++;
+      log.warn("quorum lost: serving nobody, expiring nobody",
+               {{"servers_up", Json(static_cast<int64_t>(up))}, {"needed", Json(static_cast<int64_t>(n / 2 + 1))}});
+      return Stop::kQuorumLost;
+    }
+    if (has && has_leader && idx == leader_idx) {
+      not_serving.store(true, std::memory_order_release);
+      has_leader = false;
+      election_until = now_ms() + std::max(0, cfg.election_ms);
+      log.info("leader lost: election started", {{"server", Json(static_cast<int64_t>(idx))}});
+      return Stop::kLeaderLost;
+    }
+    return Stop::kNone;
+  }
+
+  // admin_mu held; quorum mode; server idx has just gone from down to up.
+  // True if that regained the majority, which starts an election.
+  bool server_came_up_locked() {
+    size_t n = servers.size();
+    size_t up = servers_up_locked();
+    if (!(2 * up > n) || 2 * (up - 1) > n) return false;
+    election_until = now_ms() + std::max(0, cfg.election_ms);
+    log.info("quorum regained: election started", {{"servers_up", Json(static_cast<int64_t>(up))}});
+    return true;
+  }
+
+  // Resume service if it is stopped and nothing stands against it any more;
+  // otherwise the milliseconds left of the election pause, or 0 if there is
+  // nothing to wait for (already serving, or no quorum).
+  int64_t resume_serving() {
+    std::lock_guard<std::mutex> g(admin_mu);
+    if (!not_serving.load(std::memory_order_relaxed)) return 0;
+    if (!(2 * servers_up_locked() > servers.size())) return 0;
+    int64_t now = now_ms();
+    if (now < election_until) return election_until - now;
+    for (size_t i = 0; i < servers.size(); i++) {
+      if (servers[i].up) {
+        leader_idx = i;
+        break;
+      }
+    }
+    has_leader = true;
+    size_t nsess = 0;
+    {
+      // the new leader gives every session a fresh timeout
+      std::lock_guard<std::mutex> sg(session_mu);
+      for (const auto& kv : sessions) kv.second->last_touch.store(now, std::memory_order_relaxed);
+      nsess = sessions.size();
+    }
+    not_serving.store(false, std::memory_order_release);
+    log.info("leader elected: serving again, session timers restarted",
+             {{"leader", Json(static_cast<int64_t>(leader_idx))}, {"sessions", Json(static_cast<int64_t>(nsess))}});
+    return 0;
+  }
+
+  // An election has begun (election_until is set): resume when it is over.
+  void resume_after_election() {
+    int64_t wait = resume_serving();
+    if (wait > 0) loops[0]->schedule_from_any(wait, [this] { resume_after_election(); });
+  }
+
+  // Run an empty task on every IO loop and wait for it: whatever a loop was
+  // in the middle of (an accept, a drain, the sweep) has finished.
+  void loops_barrier() {
+    std::vector<std::promise<void>> done(loops.size());
+    for (size_t i = 0; i < loops.size(); i++) loops[i]->post([&done, i] { done[i].set_value(); });
+    for (auto& d : done) d.get_future().wait();
+  }
+
+  // ---------------- control (any thread but the IO loops') ----------------
 
   void kill_server(size_t idx) {
     {
@@ -2087,7 +2216,8 @@ struct Ensemble::Impl {
     }
     size_t lidx = idx % loops.size();
     std::promise<void> done;
-    loops[lidx]->post([this, idx, lidx, &done] {
+    Stop stop = Stop::kNone;
+    loops[lidx]->post([this, idx, lidx, &done, &stop] {
       {
         std::lock_guard<std::mutex> g(admin_mu);
         if (idx < servers.size() && servers[idx].up) {
@@ -2096,17 +2226,22 @@ struct Ensemble::Impl {
           ::close(s.listen_fd);
           s.listen_fd = -1;
           s.up = false;
+          if (cfg.quorum) stop = server_went_down_locked(idx);
         }
       }
       done.set_value();
     });
     done.get_future().wait();
-    // retire this server's connections on their own IO loops
+    // quorum mode, service ended: every accept from now on is refused; wait
+    // out the ones that were let in, so that they are among the victims
+    if (stop != Stop::kNone) loops_barrier();
+    // retire this server's connections (everybody's, if service ended) on
+    // their own IO loops
     std::vector<ConnPtr> victims;
     {
       std::lock_guard<std::mutex> g(conns_mu);
       for (auto& kv : conns)
-        if (kv.second->server_idx == idx) victims.push_back(kv.second);
+        if (stop != Stop::kNone || kv.second->server_idx == idx) victims.push_back(kv.second);
     }
     std::vector<std::promise<void>> vdone(victims.size());
     for (size_t i = 0; i < victims.size(); i++) {
@@ -2118,7 +2253,12 @@ struct Ensemble::Impl {
       });
     }
     for (auto& d : vdone) d.get_future().wait();
+    {
+      std::lock_guard<std::mutex> g(admin_mu);
+      dropped_conns += victims.size();
+    }
     log.info("server killed", {{"server", Json(static_cast<int64_t>(idx))}});
+    if (stop == Stop::kLeaderLost) resume_after_election();
   }
 
   void restart_server(size_t idx) {
@@ -2127,17 +2267,20 @@ struct Ensemble::Impl {
       if (idx >= servers.size()) return;
     }
     std::promise<void> done;
-    loops[idx % loops.size()]->post([this, idx, &done] {
+    bool regained = false;
+    loops[idx % loops.size()]->post([this, idx, &done, &regained] {
       {
         std::lock_guard<std::mutex> g(admin_mu);
         if (idx < servers.size() && !servers[idx].up) {
           open_listener(idx, servers[idx].port);
           log.info("server restarted", {{"server", Json(static_cast<int64_t>(idx))}});
+          if (cfg.quorum) regained = server_came_up_locked();
         }
       }
       done.set_value();
     });
     done.get_future().wait();
+    if (regained) resume_after_election();
   }
 
   // admin_mu held
@@ -2159,6 +2302,9 @@ struct Ensemble::Impl {
       victim = leader_idx;
     }
     kill_server(victim);
+    // quorum mode: kill_server has started the election itself, so that
+    // kill_server(leader()) and kill_leader() are one thing
+    if (cfg.quorum) return victim;
     std::lock_guard<std::mutex> g(admin_mu);
     if (cfg.election_ms > 0) election_until = now_ms() + cfg.election_ms;
     maybe_elect_leader_locked();
@@ -2214,6 +2360,31 @@ size_t Ensemble::kill_leader() { return impl_->kill_leader(); }
 void Ensemble::expire_session(int64_t session_id) { impl_->kill_session(session_id, /*close_conn_too=*/true); }
 
 void Ensemble::set_latency_ms(int ms) { impl_->latency_ms.store(ms); }
+
+bool Ensemble::has_quorum() const { return quorum_state().has_quorum; }
+
+QuorumState Ensemble::quorum_state() const {
+  QuorumState q;
+  std::lock_guard<std::mutex> g(impl_->admin_mu);
+  q.enabled = impl_->cfg.quorum;
+  q.servers = impl_->servers.size();
+  q.servers_up = impl_->servers_up_locked();
+  q.needed = q.servers / 2 + 1;
+  bool leader_up = impl_->leader_idx < q.servers && impl_->servers[impl_->leader_idx].up;
+  if (q.enabled) {
+    q.has_quorum = 2 * q.servers_up > q.servers;
+    q.serving = !impl_->not_serving.load(std::memory_order_relaxed);
+    q.leader = impl_->has_leader ? static_cast<int>(impl_->leader_idx) : -1;
+  } else {
+    q.has_quorum = q.servers_up > 0;
+    q.serving = q.has_quorum && now_ms() >= impl_->election_until;
+    q.leader = leader_up ? static_cast<int>(impl_->leader_idx) : -1;
+  }
+  q.losses = impl_->quorum_losses;
+  q.refused_connects = impl_->refused_connects.load(std::memory_order_relaxed);
+  q.dropped_connections = impl_->dropped_conns;
+  return q;
+}
 
 NodeInfo Ensemble::get(const std::string& path) const {
   PathRef ref = ref_of(path);

@@ -10,6 +10,8 @@
 //     ephemeral-node deletion on expiry/close, reconnect-with-same-session,
 //   - leader-kill with an optional election pause (storm testing,
 //     BASELINE.json config 4),
+//   - an optional quorum mode: no service, and no session expiry, below a
+//     majority of servers,
 //   - per-response latency injection,
 //   - one-shot data/child watches (Binder-style readers).
 //
@@ -51,6 +53,9 @@ struct EnsembleConfig {
   // parallelism is independent of ensemble size: connections are assigned
   // round-robin across the pool regardless of which server accepted them.
   int io_threads = 0;
+  // Quorum mode (off by default): below a majority of servers the ensemble
+  // serves nobody and expires nobody; see "Quorum mode" in ensemble.cpp.
+  bool quorum = false;
   LogLevel log_level = LogLevel::Warn;
 };
 
@@ -70,6 +75,25 @@ struct NodeStoreLayout {
   std::vector<size_t> classes;  // block sizes, ascending; larger blocks are never cached
 };
 
+// Quorum introspection (Ensemble::quorum_state). With the mode off the
+// ensemble "has quorum" while any server is up.
+struct QuorumState {
+  bool enabled = false;
+  size_t servers = 0;
+  size_t servers_up = 0;
+  size_t needed = 0;      // servers / 2 + 1
+  bool has_quorum = false;
+  bool serving = false;   // has quorum and no election pause is running
+  int leader = -1;        // index, or -1 while there is none
+  uint64_t losses = 0;    // times quorum was lost
+  // connections closed at accept or handshake because the ensemble was not
+  // serving (an election pause, or no quorum)
+  uint64_t refused_connects = 0;
+  // connections closed by kill_server / kill_leader, whether they were the
+  // killed server's own or everybody's (quorum or leader lost)
+  uint64_t dropped_connections = 0;
+};
+
 class Ensemble {
  public:
   explicit Ensemble(EnsembleConfig cfg);
@@ -86,7 +110,10 @@ class Ensemble {
   std::string connect_string() const;  // "host:port,host:port,..."
 
   // --- fault injection / control (thread-safe) ---
-  void kill_server(size_t idx);      // close listener + connections; sessions persist
+  // close listener + connections; sessions persist. In quorum mode, losing
+  // the majority or the leader drops every server's connections before this
+  // returns (call it from outside the IO loops, like all of this block).
+  void kill_server(size_t idx);
   void restart_server(size_t idx);   // re-listen on the same port
   bool server_up(size_t idx) const;
   size_t leader() const;
@@ -107,6 +134,8 @@ class Ensemble {
   // zero ones left out; plus "node_blocks_cached", the number of released
   // node blocks the shards currently hold for reuse (always present)
   std::map<std::string, uint64_t> counters() const;
+  bool has_quorum() const;
+  QuorumState quorum_state() const;
   static NodeStoreLayout node_store_layout();
   // Structural audit of the whole tree (parent/sibling links, counts, data
   // placement, hashes and buckets, ephemeral ownership against the sessions,

@@ -38,6 +38,8 @@ int main(int argc, char** argv) {
       cfg.latency_ms = atoi(argv[++i]);
     } else if (!strcmp(argv[i], "--election-ms") && i + 1 < argc) {
       cfg.election_ms = atoi(argv[++i]);
+    } else if (!strcmp(argv[i], "--quorum")) {
+      cfg.quorum = true;
     } else if (!strcmp(argv[i], "-b") && i + 1 < argc) {
       cfg.bind_host = argv[++i];
     } else if (!strcmp(argv[i], "-v")) {
@@ -45,7 +47,8 @@ int main(int argc, char** argv) {
     } else {
       fprintf(stderr,
               "usage: %s [-n NSERVERS] [-p PORT]... [-b BINDHOST] [--tick-ms MS] "
-              "[--latency-ms MS] [--election-ms MS] [-v]\n",
+              "[--latency-ms MS] [--election-ms MS] [--quorum] [-v]\n"
+              "  --quorum  no service and no session expiry below a majority of servers\n",
               argv[0]);
       return 1;
     }

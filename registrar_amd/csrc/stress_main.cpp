@@ -16,7 +16,10 @@
 //   - then a crossed-parents phase on a two-loop ensemble of its own (see
 //     crossed_phase): the locks a drain carries, under contention,
 //   - then the tree's lock type on its own (see treelock_phase): eight
-//     threads, one TreeLock, one plain counter.
+//     threads, one TreeLock, one plain counter,
+//   - then a quorum phase on a 3-server quorum-mode ensemble of its own (see
+//     quorum_phase): registered clients heartbeat while the chaos thread
+//     crosses the majority boundary in both directions.
 // At the end, with every client closed and every session gone, the tree must
 // pass Ensemble::audit() and hold no ephemeral.
 // Exit code 0 = every cycle behaved and the end state is sound; sanitizers
@@ -234,6 +237,198 @@ bool treelock_phase() {
          static_cast<unsigned long long>(kThreads * kPerThread), static_cast<unsigned long long>(tried.load()));
   return !held && counter == kThreads * kPerThread;
 }
+
+// Quorum phase, on a 3-server quorum-mode ensemble of its own. Each client
+// registers once and then heartbeats, re-registering only if its session was
+// lost. The chaos thread meanwhile loses the majority and regains it, kills
+// the leader during the election pause that follows, kills the leader with
+// the majority intact, and does a rolling restart, over and over. Whenever
+// the ensemble is below a majority the chaos thread also checks that zxid
+// stands still. At the end, with every server back, the ensemble serving and
+// every client connected (so no expiry is in flight), audit() must be empty
+// and every client's znodes present. Returns true when all of that held.
+bool quorum_phase(int nclients, int seconds, const Logger& log) {
+  zk::EnsembleConfig ecfg;
+  ecfg.ports = {0, 0, 0};
+  ecfg.tick_ms = 50;
+  ecfg.min_session_timeout_ms = 300;
+  ecfg.election_ms = 100;
+  ecfg.quorum = true;
+  ecfg.log_level = LogLevel::Error;
+  zk::Ensemble ens(ecfg);
+  ens.start();
+  std::vector<int> ports = ens.ports();
+
+  std::atomic<bool> stop{false};
+  std::atomic<uint64_t> heartbeats{0}, registers{0}, bad{0};
+  std::atomic<int> settled_count{0};
+  std::atomic<bool> release{false};
+  std::vector<std::vector<std::string>> held(static_cast<size_t>(nclients));
+  std::vector<int> settled(static_cast<size_t>(nclients), 0);
+
+  auto client_fn = [&](int idx) {
+    RegistrationConfig reg;
+    reg.domain = "q" + std::to_string(idx) + ".quorum.stress.test";
+    reg.type = "host";
+    reg.admin_ip = "127.0.0.1";
+    reg.hostname = "h" + std::to_string(idx);
+    reg.settle_ms = 0;
+    for (int a = 0; a < 20; a++) reg.aliases.push_back("a" + std::to_string(a) + "." + reg.domain);
+    zk::RetryPolicy rp;
+    rp.max_attempts = 1;
+    rp.initial_delay_ms = 10;
+
+    std::unique_ptr<zk::ZkClient> client;
+    std::vector<std::string> znodes;
+    // one step towards "connected, registered, heartbeat answered"
+    auto step = [&]() -> bool {
+      if (!client || client->state() == zk::SessionState::Expired || client->state() == zk::SessionState::Closed) {
+        if (client) client->close();
+        znodes.clear();
+        zk::ZkClientConfig ccfg;
+        for (int p : ports) ccfg.servers.push_back({"127.0.0.1", p});
+        ccfg.session_timeout_ms = 4000;
+        ccfg.connect_timeout_ms = 1000;
+        ccfg.connect_initial_delay_ms = 20;
+        ccfg.connect_max_delay_ms = 100;
+        ccfg.log_level = LogLevel::Fatal;
+        client = std::make_unique<zk::ZkClient>(std::move(ccfg), log);
+        client->start();
+      }
+      if (!client->wait_connected(200)) return false;
+      if (znodes.empty()) {
+        RegisterResult res = register_node(*client, reg, log);
+        if (res.rc != zk::kZOk) return false;  // the ensemble went away mid-register
+        znodes = res.znodes();
+        registers.fetch_add(1);
+      }
+      int rc = client->heartbeat(znodes, rp, nullptr);
+      if (rc == zk::kZOk) {
+        heartbeats.fetch_add(1);
+        return true;
+      }
+      if (rc == zk::kZNoNode)
+        znodes.clear();  // the session was lost and its znodes with it: register again
+      else if (rc != zk::kZConnectionLoss && rc != zk::kZSessionExpired)
+        bad.fetch_add(1);
+      return false;
+    };
+    while (!stop.load()) {
+      step();
+      std::this_thread::sleep_for(std::chrono::milliseconds(10));
+    }
+    // the chaos thread has restored every server by now: settle
+    auto deadline = std::chrono::steady_clock::now() + std::chrono::seconds(20);
+    bool ok = false;
+    while (!(ok = step()) && std::chrono::steady_clock::now() < deadline)
+      std::this_thread::sleep_for(std::chrono::milliseconds(10));
+    held[static_cast<size_t>(idx)] = znodes;
+    settled[static_cast<size_t>(idx)] = ok ? 1 : 0;
+    settled_count.fetch_add(1);  // publishes the two writes above
+    // stay connected until the end state has been checked
+    while (!release.load()) std::this_thread::sleep_for(std::chrono::milliseconds(10));
+    if (client) client->close();
+  };
+
+  std::atomic<uint64_t> crossings{0};
+  auto nap = [](int ms) { std::this_thread::sleep_for(std::chrono::milliseconds(ms)); };
+  auto restore = [&] {
+    for (size_t i = 0; i < 3; i++)
+      if (!ens.server_up(i)) ens.restart_server(i);
+  };
+  auto lost = [&] {
+    if (!ens.has_quorum()) crossings.fetch_add(1);
+  };
+  // below a majority nothing may commit
+  auto frozen = [&](int ms) {
+    int64_t z = ens.zxid();
+    nap(ms);
+    if (!ens.has_quorum() && ens.zxid() != z) bad.fetch_add(1);
+  };
+  auto chaos_fn = [&] {
+    while (!stop.load()) {
+      nap(250);
+      // lose the majority, hold, regain it
+      ens.kill_server(2);
+      ens.kill_server(1);
+      lost();
+      frozen(200);
+      ens.restart_server(1);
+      // ... and kill the leader during the election pause: if the last
+      // leader is the server still up, this loses the majority again
+      ens.kill_leader();
+      lost();
+      frozen(100);
+      restore();
+      nap(300);
+      // leader loss with the majority intact, then a second server lost
+      // during the pause: below a majority with an election pending
+      ens.kill_leader();
+      for (size_t i = 0; i < 3; i++) {
+        if (ens.server_up(i)) {
+          ens.kill_server(i);
+          break;
+        }
+      }
+      lost();
+      frozen(150);
+      restore();
+      nap(200);
+      // rolling restart: never below a majority
+      for (size_t i = 0; i < 3 && !stop.load(); i++) {
+        ens.kill_server(i);
+        nap(150);
+        ens.restart_server(i);
+        nap(150);
+      }
+    }
+    restore();
+  };
+
+  std::vector<std::thread> threads;
+  for (int i = 0; i < nclients; i++) threads.emplace_back(client_fn, i);
+  std::thread chaos(chaos_fn);
+  std::this_thread::sleep_for(std::chrono::seconds(seconds));
+  stop.store(true);
+  chaos.join();
+  // every server is back; wait for the election to end and for every client
+  // to have had a heartbeat answered on a registered session
+  auto deadline = std::chrono::steady_clock::now() + std::chrono::seconds(30);
+  while ((!ens.quorum_state().serving || settled_count.load() < nclients) &&
+         std::chrono::steady_clock::now() < deadline)
+    nap(10);
+  zk::QuorumState qs = ens.quorum_state();
+  bool all_settled = settled_count.load() == nclients;
+  size_t total = 0, missing = 0;
+  if (all_settled) {
+    for (int i = 0; i < nclients; i++) {
+      if (!settled[static_cast<size_t>(i)]) all_settled = false;
+      for (const auto& z : held[static_cast<size_t>(i)]) {
+        total++;
+        if (!ens.get(z).exists) missing++;
+      }
+    }
+  }
+  // every session is connected and heartbeating: no expiry is in flight
+  std::vector<std::string> violations = ens.audit();
+  size_t eph = ens.ephemeral_count();
+  release.store(true);
+  for (auto& t : threads) t.join();
+  ens.stop();
+
+  printf("stress: quorum phase: %llu heartbeats, %llu registers by %d clients, %llu majority losses seen, "
+         "%llu counted, %llu refused connects, %llu dropped connections, %llu unexpected, %zu of %zu znodes missing, "
+         "%zu ephemerals\n",
+         static_cast<unsigned long long>(heartbeats.load()), static_cast<unsigned long long>(registers.load()),
+         nclients, static_cast<unsigned long long>(crossings.load()), static_cast<unsigned long long>(qs.losses),
+         static_cast<unsigned long long>(qs.refused_connects), static_cast<unsigned long long>(qs.dropped_connections),
+         static_cast<unsigned long long>(bad.load()), missing, total, eph);
+  for (const auto& v : violations) printf("stress: quorum phase: audit: %s\n", v.c_str());
+  if (!all_settled) printf("stress: quorum phase: not every client got back to a registered, answered heartbeat\n");
+  return qs.serving && qs.has_quorum && all_settled && violations.empty() && bad.load() == 0 && missing == 0 &&
+         total == static_cast<size_t>(nclients) * 21 && eph == total && qs.losses == crossings.load() &&
+         crossings.load() > 0 && heartbeats.load() > 0;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -395,6 +590,7 @@ int main(int argc, char** argv) {
   // crossed parents (carried locks under contention), on its own ensemble
   bool crossed_ok = crossed_secs <= 0 || crossed_phase(crossed_secs, log);
   bool treelock_ok = treelock_phase();
+  bool quorum_ok = seconds <= 0 || quorum_phase(nclients, std::max(3, seconds / 2), log);
 
   // End state. Every client is closed, so every session ends: by its close,
   // or (where the close was lost to a killed server) by the expiry sweep. A
@@ -440,5 +636,6 @@ int main(int argc, char** argv) {
   bool behaved = cycles.load() > 0 && failures.load() < cycles.load() / 4 + 16;
   if (!crossed_ok) printf("stress: the crossed-parents phase failed\n");
   if (!treelock_ok) printf("stress: the tree lock phase failed\n");
-  return (behaved && sound && crossed_ok && treelock_ok) ? 0 : 1;
+  if (!quorum_ok) printf("stress: the quorum phase failed\n");
+  return (behaved && sound && crossed_ok && treelock_ok && quorum_ok) ? 0 : 1;
 }
