@@ -344,10 +344,20 @@ PYBIND11_MODULE(_core, m) {
            py::arg("paths"), py::arg("data") = py::bytes(""), py::arg("ephemeral") = false)
       .def("delete_many", &zk::ZkClient::delete_many, py::call_guard<py::gil_scoped_release>())
       .def("exists_many",
-           [](zk::ZkClient& c, const std::vector<std::string>& paths) {
-             py::gil_scoped_release rel;
-             return c.exists_many(paths, nullptr);
-           })
+           [](zk::ZkClient& c, const std::vector<std::string>& paths, bool stats) -> py::object {
+             // the rcs alone, or with stats=True (rcs, [Stat dict per path])
+             std::vector<zk::Stat> sts;
+             std::vector<int> rcs;
+             {
+               py::gil_scoped_release rel;
+               rcs = c.exists_many(paths, stats ? &sts : nullptr);
+             }
+             if (!stats) return py::cast(rcs);
+             py::list out;
+             for (const auto& st : sts) out.append(stat_to_dict(st));
+             return py::make_tuple(rcs, out);
+           },
+           py::arg("paths"), py::arg("stats") = false)
       .def("multi",
            [](zk::ZkClient& c, const py::list& ops) {
              std::vector<zk::ZkClient::MixedOp> mops;

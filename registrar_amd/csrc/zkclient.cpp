@@ -70,7 +70,10 @@ struct ZkClient::Impl {
   struct Pending {
     int32_t xid;  // single op: its xid; batch: the FIRST xid of the run
     int32_t op;
-    // rc + body reader (null unless rc==kZOk and the op has a body)
+    // rc + body reader (null unless rc==kZOk and the op has a body). May
+    // throw while decoding the body, and only then: before it completes its
+    // caller or touches client state. handle_frame answers a throw by calling
+    // it once more with (kZConnectionLoss, null), which must not throw.
     std::function<void(int rc, JuteReader* r)> done;
     // batch record (submit_template): `count` consecutive xids answered in
     // order; reply i's rc is written straight into (*rcs)[i] — no callback,
@@ -291,6 +294,14 @@ struct ZkClient::Impl {
       return;
     }
     int64_t delay = bo.next_delay();
+    if (have_session) {
+      // a session is waiting: one turn through the whole server list has to
+      // fit in a third of its timeout, or a client asleep when service comes
+      // back, with dead addresses still ahead of the live one, returns after
+      // the servers have expired it
+      int64_t turn = negotiated_timeout / (3 * static_cast<int64_t>(cfg.servers.size()));
+      delay = std::min(delay, std::max(turn, reconnect_backoff.initial_ms));
+    }
     int64_t attempt = bo.attempt;  // 1-based after next_delay()
     // per-attempt log level escalates info→warn→error (reference lib/zk.js:104-119)
     std::vector<JsonMember> fields{{"attempt", Json(attempt)}, {"delay", Json(delay)}, {"reason", Json(why)},
@@ -310,6 +321,14 @@ struct ZkClient::Impl {
   }
 
   void on_connection_lost(const char* why) {
+    if (phase != Phase::Ready) {
+      // ended before the handshake completed (EOF, socket error, malformed
+      // ConnectResponse): nothing was connected, so this is a failed attempt
+      // and waits out its backoff like a refused connection. Retrying at once
+      // is a busy loop against a peer that accepts and closes.
+      on_connect_failed(why);
+      return;
+    }
     log.warn("zookeeper: disconnected", {{"reason", Json(why)}});
     teardown_socket();
     fail_all_pending(kZConnectionLoss);
@@ -461,7 +480,9 @@ struct ZkClient::Impl {
 
       ReplyHeader hdr;
       hdr.deserialize(r);
-      if (hdr.zxid > 0) last_zxid = hdr.zxid;
+      // the highest seen, not the latest: lastZxidSeen in a reconnect tells the
+      // next server how far this client has read, and must never step back
+      if (hdr.zxid > last_zxid) last_zxid = hdr.zxid;
       if (hdr.xid == kXidWatcherEvent) {
         WatcherEvent ev;
         ev.deserialize(r);
@@ -529,7 +550,19 @@ struct ZkClient::Impl {
       if (p.done) {
         // the reader is passed even on error replies: multi responses carry
         // per-op error results in the body (callbacks gate on rc themselves)
-        p.done(hdr.err, &r);
+        try {
+          p.done(hdr.err, &r);
+        } catch (const std::exception& e) {
+          // the body did not decode. p is off the queue already, so
+          // fail_all_pending cannot reach it: complete it here, first, as the
+          // oldest request. Callbacks decode before they complete their
+          // caller, so this is the one completion.
+          log.error("zookeeper: malformed reply body",
+                    {{"xid", Json(static_cast<int64_t>(p.xid))}, {"err", Json(e.what())}});
+          p.done(kZConnectionLoss, nullptr);
+          on_connection_lost("malformed frame");
+          return false;
+        }
       }
       return true;
     } catch (const std::exception& e) {
@@ -541,18 +574,25 @@ struct ZkClient::Impl {
 
   // ---------------- ping ----------------
 
-  void schedule_ping() {
+  // A ping every third of the session timeout; a server silent for more than
+  // two thirds of it is presumed dead. Against a silent server the second tick
+  // falls on the cut itself, give or take a millisecond of timer lateness, so
+  // a tick whose successor would pass the cut is followed by one just behind
+  // the cut instead: the loss shows at 2T/3, not at T when the session is gone.
+  void schedule_ping(int64_t idle = 0) {
     int64_t interval = std::max<int64_t>(negotiated_timeout / 3, 100);
-    ping_timer = loop.schedule(interval, [this] {
+    int64_t cut = negotiated_timeout * 2 / 3;
+    if (idle + interval > cut) interval = std::max<int64_t>(cut + 1 - idle, 1);
+    ping_timer = loop.schedule(interval, [this, cut] {
       ping_timer = 0;
       if (phase != Phase::Ready) return;
-      // server silent for 2/3 of the session timeout ⇒ presume dead, move on
-      if (now_ms() - last_recv > negotiated_timeout * 2 / 3) {
+      int64_t idle = now_ms() - last_recv;
+      if (idle > cut) {
         on_connection_lost("ping timeout");
         return;
       }
       submit(kXidPing, kOpPing, [](JuteWriter&) {}, nullptr);
-      schedule_ping();
+      schedule_ping(idle);
     });
   }
 
@@ -777,6 +817,14 @@ void ZkClient::aexists(const std::string& path, bool watch, StatCallback cb) {
     Impl* impl = impl_.get();
     impl_->submit_op(kOpExists, [req](JuteWriter& w) { req.serialize(w); },
                      [cb, impl, req](int rc, JuteReader* r) {
+                       // decode first: a body that throws must leave no
+                       // trace (handle_frame then completes with an error)
+                       Stat st;
+                       if (cb && rc == kZOk && r) {
+                         ExistsResponse resp;
+                         resp.deserialize(*r);
+                         st = resp.stat;
+                       }
                        if (req.watch) {
                          // exists registers a watch on present AND absent
                          // nodes (created-event semantics)
@@ -785,14 +833,7 @@ void ZkClient::aexists(const std::string& path, bool watch, StatCallback cb) {
                          else if (rc == kZNoNode)
                            impl->exist_watch_paths.insert(req.path);
                        }
-                       if (!cb) return;
-                       Stat st;
-                       if (rc == kZOk && r) {
-                         ExistsResponse resp;
-                         resp.deserialize(*r);
-                         st = resp.stat;
-                       }
-                       cb(rc, st);
+                       if (cb) cb(rc, st);
                      });
   });
 }
@@ -805,17 +846,16 @@ void ZkClient::aget(const std::string& path, bool watch, DataCallback cb) {
     Impl* impl = impl_.get();
     impl_->submit_op(kOpGetData, [req](JuteWriter& w) { req.serialize(w); },
                      [cb, impl, req](int rc, JuteReader* r) {
-                       if (req.watch && rc == kZOk) impl->data_watch_paths.insert(req.path);
-                       if (!cb) return;
                        std::string data;
                        Stat st;
-                       if (rc == kZOk && r) {
+                       if (cb && rc == kZOk && r) {
                          GetDataResponse resp;
                          resp.deserialize(*r);
                          data = resp.data;
                          st = resp.stat;
                        }
-                       cb(rc, data, st);
+                       if (req.watch && rc == kZOk) impl->data_watch_paths.insert(req.path);
+                       if (cb) cb(rc, data, st);
                      });
   });
 }
@@ -848,15 +888,14 @@ void ZkClient::achildren(const std::string& path, bool watch, ChildrenCallback c
     Impl* impl = impl_.get();
     impl_->submit_op(kOpGetChildren, [req](JuteWriter& w) { req.serialize(w); },
                      [cb, impl, req](int rc, JuteReader* r) {
-                       if (req.watch && rc == kZOk) impl->child_watch_paths.insert(req.path);
-                       if (!cb) return;
                        std::vector<std::string> children;
-                       if (rc == kZOk && r) {
+                       if (cb && rc == kZOk && r) {
                          GetChildrenResponse resp;
                          resp.deserialize(*r);
                          children = std::move(resp.children);
                        }
-                       cb(rc, children);
+                       if (req.watch && rc == kZOk) impl->child_watch_paths.insert(req.path);
+                       if (cb) cb(rc, children);
                      });
   });
 }
