@@ -6,7 +6,8 @@ SRCDIR := registrar_amd/csrc
 BINDIR := bin
 
 CORE_SRCS := $(SRCDIR)/ensemble.cpp $(SRCDIR)/zkclient.cpp $(SRCDIR)/registrar.cpp \
-             $(SRCDIR)/health.cpp $(SRCDIR)/orchestrator.cpp $(SRCDIR)/gpu.cpp
+             $(SRCDIR)/health.cpp $(SRCDIR)/orchestrator.cpp $(SRCDIR)/gpu.cpp \
+             $(SRCDIR)/resolver.cpp
 HDRS := $(wildcard $(SRCDIR)/*.hpp)
 
 .PHONY: all ext daemon test check clean tsan asan stress hotpath hotpath-prof

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""A Binder-style consumer: discover live instances of a service by reading
-the records registrar writes, and follow changes with watches.
+"""A Binder-style consumer: discover live instances of a service through a
+Resolver, which reads the records registrar writes once and keeps its view
+current with watches.
 
 Usage:
     python examples/consumer.py --servers HOST:PORT[,HOST:PORT...] DOMAIN
+        [--follow] [--local-address A]
 
 Example (against a demo ensemble + daemon):
     ./bin/zkensembled -n 1           # note the port
@@ -11,7 +13,6 @@ Example (against a demo ensemble + daemon):
     python examples/consumer.py --servers 127.0.0.1:PORT test.coal.example.com
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -21,63 +22,53 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import registrar_amd as ra  # noqa: E402
 
 
+def show(domain, snap):
+    svc = snap["service"]
+    if svc:
+        print("SRV %s.%s.%s port=%s ttl=%s" % (svc["srvce"], svc["proto"], domain, svc["port"], svc.get("ttl")))
+    print("%d live instance(s) under %s%s:" % (len(snap["hosts"]), ra.domain_to_path(domain),
+                                               " (stale)" if snap["stale"] else ""))
+    for h in snap["hosts"]:  # same-node instances first
+        gpu = h["gpu"]
+        extra = " xgmiRank=%s gpu=%s" % (gpu["xgmiRank"], gpu["index"]) if gpu else ""
+        print("  %-24s %-15s session=0x%x%s%s"
+              % (h["name"], h["address"], h["ephemeral_owner"], extra, " local" if h["local"] else ""))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--servers", required=True)
     ap.add_argument("domain")
     ap.add_argument("--follow", action="store_true", help="keep watching for changes")
+    ap.add_argument("--local-address", default="", help="this node's address: its instances are listed first")
     args = ap.parse_args()
 
-    servers = []
-    for hp in args.servers.split(","):
-        host, port = hp.rsplit(":", 1)
-        servers.append((host, int(port)))
-    path = ra.domain_to_path(args.domain)
-
-    c = ra.ZkClient(servers=servers, connect_max_attempts=5)
-    c.start()
-    if not c.wait_connected(15000):
-        print("could not connect", file=sys.stderr)
-        return 1
-
-    def show():
-        rc, data, st = c.get(path)
-        if rc == 0 and data:
-            rec = json.loads(data)
-            if rec.get("type") == "service":
-                svc = rec["service"]["service"]
-                print("SRV %s.%s.%s port=%s ttl=%s"
-                      % (svc["srvce"], svc["proto"], args.domain, svc["port"], svc["ttl"]))
-        rc, children = c.get_children(path, watch=args.follow)
-        if rc != 0:
-            print("(no such domain path: %s)" % path)
-            return
-        live = []
-        for ch in children:
-            rc, data, st = c.get("%s/%s" % (path, ch))
-            if rc != 0:
-                continue
-            rec = json.loads(data)
-            addr = rec.get("address")
-            gpu = rec.get(rec.get("type", ""), {}).get("gpu")
-            live.append((ch, addr, st["ephemeralOwner"], gpu))
-        print("%d live instance(s) under %s:" % (len(live), path))
-        for name, addr, owner, gpu in live:
-            extra = " xgmiRank=%s gpu=%s" % (gpu["xgmiRank"], gpu["index"]) if gpu else ""
-            print("  %-24s %-15s session=0x%x%s" % (name, addr, owner, extra))
-
-    show()
-    if args.follow:
-        print("watching for membership changes (ctrl-c to stop)...")
-        try:
+    servers = [(hp.rsplit(":", 1)[0], int(hp.rsplit(":", 1)[1])) for hp in args.servers.split(",")]
+    r = ra.Resolver(servers=servers, local_address=args.local_address)
+    r.start()
+    try:
+        snap = r.lookup(args.domain, 15000, local_first=True)
+        if snap["status"] == "unavailable":
+            print("could not connect", file=sys.stderr)
+            return 1
+        if snap["status"] == "absent":
+            print("(no such domain path: %s)" % ra.domain_to_path(args.domain))
+        else:
+            show(args.domain, snap)
+        if args.follow:
+            print("watching for membership changes (ctrl-c to stop)...")
+            r.poll_events()
             while True:
-                for ev in c.poll_watches():
-                    print("-- change: %s %s" % (ev["type"], ev["path"]))
-                    show()
+                events = r.poll_events()
+                for ev in events:
+                    print("-- %s %s" % (ev["type"], ev["name"] or ev["domain"]))
+                if events:
+                    show(args.domain, r.snapshot(args.domain, local_first=True))
                 time.sleep(0.2)
-        except KeyboardInterrupt:
-            pass
-    c.close()
+    except KeyboardInterrupt:
+        pass
+    finally:
+        r.stop()
     return 0
 
 

@@ -42,6 +42,7 @@ from registrar_amd._core import (  # noqa: F401
     HealthCheck,
     Orchestrator,
     PreparedRegistration,
+    Resolver,
     ZkClient,
     build_host_record,
     build_node_list,
@@ -74,6 +75,7 @@ __all__ = [
     "HealthCheck",
     "Orchestrator",
     "PreparedRegistration",
+    "Resolver",
     "ZkClient",
     "build_host_record",
     "build_node_list",

@@ -11,9 +11,15 @@ Subcommands:
                                                synthetic ensemble or real ZK)
   gpus                                         show KFD GPU topology/xGMI ranks
   check    -f CONFIG                           validate a config file
-  binder   --servers HOST:PORT[,...] [--port N]  serve DNS A/SRV answers from
+  binder   --servers HOST:PORT[,...] [--port N] [--cache]
+                                               serve DNS A/SRV answers from
                                                the registration tree
-                                               (binder_lite)
+                                               (binder_lite; --cache: from a
+                                               watch-maintained Resolver view)
+  resolve  --servers HOST:PORT[,...] DOMAIN [--follow] [--local-address A]
+                                               print a domain's live hosts as
+                                               one JSON line per snapshot, and
+                                               with --follow one per event
   verify   -f CONFIG                           pre-deployment smoke: connect,
                                                register, heartbeat, unregister
 """
@@ -66,10 +72,11 @@ def cmd_ensemble(args):
     ens = ra.Ensemble(servers=args.n, ports=args.port or [], log_level="info" if args.verbose else "warn",
                       quorum=args.quorum)
     ens.start()
-    print(json.dumps({"ports": ens.ports(), "connect": ens.connect_string()}), flush=True)
+    # handlers first: whoever reads the line below may signal at once
     stop = []
     signal.signal(signal.SIGINT, lambda *_: stop.append(1))
     signal.signal(signal.SIGTERM, lambda *_: stop.append(1))
+    print(json.dumps({"ports": ens.ports(), "connect": ens.connect_string()}), flush=True)
     try:
         while not stop:
             time.sleep(0.1)
@@ -136,17 +143,59 @@ def cmd_gpus(_args):
 def cmd_binder(args):
     from registrar_amd.binder_lite import BinderLite
 
-    b = BinderLite(_parse_servers(args.servers), host=args.host, port=args.port)
+    b = BinderLite(_parse_servers(args.servers), host=args.host, port=args.port, cache=args.cache)
     b.start()
-    print(json.dumps({"dns": "%s:%d" % b.address}), flush=True)
     stop = []
     signal.signal(signal.SIGINT, lambda *_: stop.append(1))
     signal.signal(signal.SIGTERM, lambda *_: stop.append(1))
+    print(json.dumps({"dns": "%s:%d" % b.address, "cache": bool(args.cache)}), flush=True)
     try:
         while not stop:
             time.sleep(0.1)
     finally:
         b.stop()
+    return 0
+
+
+def snapshot_line(domain, snap):
+    """One JSON-able dict per snapshot: what a consumer needs, no raw payloads."""
+    return {
+        "domain": domain,
+        "status": snap.get("status", "ok" if snap["exists"] else "absent"),
+        "generation": snap["generation"],
+        "stale": snap["stale"],
+        "service": snap["service"],
+        "hosts": [{k: h[k] for k in ("name", "address", "ttl", "ports", "gpu", "local")} for h in snap["hosts"]],
+    }
+
+
+def cmd_resolve(args):
+    import registrar_amd as ra
+
+    r = ra.Resolver(servers=_parse_servers(args.servers), local_address=args.local_address)
+    r.start()
+    stop = []
+    signal.signal(signal.SIGINT, lambda *_: stop.append(1))
+    signal.signal(signal.SIGTERM, lambda *_: stop.append(1))
+    try:
+        snap = r.lookup(args.domain, args.timeout * 1000, local_first=True)
+        print(json.dumps(snapshot_line(args.domain, snap)), flush=True)
+        if not args.follow:
+            return 0 if snap["status"] == "ok" else 1
+        r.poll_events()  # the first build is the line above
+        while not stop:
+            events = r.poll_events()
+            for ev in events:
+                print(json.dumps({"event": ev["type"], "domain": ev["domain"], "name": ev["name"],
+                                  "generation": ev["generation"]}), flush=True)
+            if events:
+                print(json.dumps(snapshot_line(args.domain, r.snapshot(args.domain, local_first=True))),
+                      flush=True)
+            elif not r.domains():
+                r.watch(args.domain)  # absent or dropped: a view starts once the domain exists
+            time.sleep(0.2)
+    finally:
+        r.stop()
     return 0
 
 
@@ -254,7 +303,18 @@ def main(argv=None):
     b.add_argument("--servers", required=True, help="ZK host:port[,host:port...]")
     b.add_argument("--host", default="127.0.0.1")
     b.add_argument("--port", type=int, default=5353)
+    b.add_argument("--cache", action="store_true",
+                   help="answer from a watch-maintained view: no ZooKeeper read per query, "
+                        "and the last view is served while the ensemble is unreachable")
     b.set_defaults(fn=cmd_binder)
+
+    r = sub.add_parser("resolve", help="print a domain's live hosts (one JSON line per snapshot or event)")
+    r.add_argument("--servers", required=True, help="ZK host:port[,host:port...]")
+    r.add_argument("domain")
+    r.add_argument("--follow", action="store_true", help="keep printing events and snapshots")
+    r.add_argument("--local-address", default="", help="hosts at this address are flagged local and come first")
+    r.add_argument("--timeout", type=int, default=15, help="seconds to wait for the first view")
+    r.set_defaults(fn=cmd_resolve)
 
     args = ap.parse_args(argv)
     return args.fn(args)

@@ -23,6 +23,14 @@ Transport: UDP with classic 512-byte truncation (TC bit set, whole RRs only)
 plus a TCP listener on the same port (RFC 1035 2-byte length framing) so a
 truncated answer set — easy at 1k records per domain — is retried over TCP
 and served complete.
+
+Two ways to read the tree. By default every query reads it directly: one
+getData for the service record, one getChildren, one getData per child. With
+`cache=True` the records come from a `Resolver` view that watches keep current
+(docs/architecture.md, "Resolver"): after the first query of a domain a query
+costs no ZooKeeper round trip at all, and while the ensemble is unreachable
+the last view is still served. The answers of the two modes are the same
+bytes for the same tree.
 """
 import socket
 import struct
@@ -68,11 +76,20 @@ class BinderLite:
     """UDP DNS responder backed by a ZkClient (works against the synthetic
     ensemble or a real ZooKeeper)."""
 
-    def __init__(self, servers, host="127.0.0.1", port=0):
-        self._client = ra.ZkClient(servers=servers, session_timeout_ms=30000)
-        self._client.start()
-        if not self._client.wait_connected(15000):
-            raise RuntimeError("binder_lite: cannot connect to ZooKeeper")
+    def __init__(self, servers, host="127.0.0.1", port=0, cache=False, session_timeout_ms=30000,
+                 lookup_timeout_ms=5000):
+        self._client = None
+        self._resolver = None
+        self._lookup_timeout_ms = lookup_timeout_ms
+        if cache:
+            self._resolver = ra.Resolver(servers=servers, session_timeout_ms=session_timeout_ms)
+            self._resolver.start()
+            self._lookup = self._lookup_cached
+        else:
+            self._client = ra.ZkClient(servers=servers, session_timeout_ms=session_timeout_ms)
+            self._client.start()
+            if not self._client.wait_connected(15000):
+                raise RuntimeError("binder_lite: cannot connect to ZooKeeper")
         self._sock = socket.socket(socket.AF_INET, socket.SOCK_DGRAM)
         self._sock.bind((host, port))
         self._sock.settimeout(0.2)
@@ -102,7 +119,15 @@ class BinderLite:
         self._tthread.join()
         self._sock.close()
         self._tsock.close()
-        self._client.close()
+        if self._client:
+            self._client.close()
+        if self._resolver:
+            self._resolver.stop()
+
+    @property
+    def resolver(self):
+        """The Resolver behind a cache=True binder (None otherwise)."""
+        return self._resolver
 
     # ---- record lookup (the registrar data contract) ----
 
@@ -143,6 +168,12 @@ class BinderLite:
                 "ports": typed.get("ports") or ([service["port"]] if service else []),
             })
         return hosts, service, path
+
+    def _lookup_cached(self, domain):
+        snap = self._resolver.lookup(domain, self._lookup_timeout_ms)
+        if snap["status"] != "ok":
+            return None, None, None  # absent or unreachable with no view: NXDOMAIN
+        return snap["hosts"], snap["service"], None
 
     # ---- DNS wire ----
 

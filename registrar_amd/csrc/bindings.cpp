@@ -16,6 +16,7 @@
 #include "log.hpp"
 #include "orchestrator.hpp"
 #include "registrar.hpp"
+#include "resolver.hpp"
 #include "zkclient.hpp"
 
 namespace py = pybind11;
@@ -97,6 +98,33 @@ zk::ZkClientConfig client_config_from_args(const std::vector<std::pair<std::stri
   cfg.randomize_start = randomize_start;
   cfg.log_level = level_from(log_level);
   return cfg;
+}
+
+py::dict snapshot_to_dict(const ResolverSnapshot& s) {
+  py::object loads = py::module_::import("json").attr("loads");
+  py::dict d;
+  d["exists"] = s.exists;
+  d["synced"] = s.synced;
+  d["stale"] = s.stale;
+  d["generation"] = s.generation;
+  d["service"] = s.service.present ? py::object(loads(s.service.json)) : py::object(py::none());
+  py::list hosts;
+  for (const auto& h : s.hosts) {
+    py::dict e;
+    e["name"] = h.name;
+    e["address"] = h.has_address ? py::object(py::str(h.address)) : py::object(py::none());
+    e["ttl"] = h.has_ttl ? py::object(py::int_(h.ttl)) : py::object(py::none());
+    e["ports"] = h.ports;
+    e["type"] = h.type;
+    e["gpu"] = h.gpu_json.empty() ? py::object(py::none()) : py::object(loads(h.gpu_json));
+    e["ephemeral_owner"] = h.ephemeral_owner;
+    e["mzxid"] = h.mzxid;
+    e["payload"] = py::bytes(h.payload);
+    e["local"] = h.local;
+    hosts.append(e);
+  }
+  d["hosts"] = hosts;
+  return d;
 }
 
 zk::RetryPolicy retry_from_dict(const py::dict& d) {
@@ -213,16 +241,18 @@ PYBIND11_MODULE(_core, m) {
   py::class_<zk::ZkClient>(m, "ZkClient")
       .def(py::init([](const std::vector<std::pair<std::string, int>>& servers, int session_timeout_ms,
                        int connect_timeout_ms, int64_t connect_initial_delay_ms, int64_t connect_max_delay_ms,
-                       int64_t connect_max_attempts, bool randomize_start, const std::string& log_level) {
-             return std::make_unique<zk::ZkClient>(
+                       int64_t connect_max_attempts, bool randomize_start, const std::string& log_level,
+                       bool queue_watches) {
+             zk::ZkClientConfig cfg =
                  client_config_from_args(servers, session_timeout_ms, connect_timeout_ms, connect_initial_delay_ms,
-                                         connect_max_delay_ms, connect_max_attempts, randomize_start, log_level),
-                 make_logger("zkclient", log_level));
+                                         connect_max_delay_ms, connect_max_attempts, randomize_start, log_level);
+             cfg.queue_watches = queue_watches;
+             return std::make_unique<zk::ZkClient>(std::move(cfg), make_logger("zkclient", log_level));
            }),
            py::arg("servers"), py::arg("session_timeout_ms") = 30000, py::arg("connect_timeout_ms") = 4000,
            py::arg("connect_initial_delay_ms") = 1000, py::arg("connect_max_delay_ms") = 90000,
            py::arg("connect_max_attempts") = -1, py::arg("randomize_start") = true,
-           py::arg("log_level") = "warn")
+           py::arg("log_level") = "warn", py::arg("queue_watches") = true)
       .def("start", &zk::ZkClient::start, py::call_guard<py::gil_scoped_release>())
       .def("wait_connected", &zk::ZkClient::wait_connected, py::arg("timeout_ms") = -1,
            py::call_guard<py::gil_scoped_release>())
@@ -358,6 +388,21 @@ PYBIND11_MODULE(_core, m) {
              return py::make_tuple(rcs, out);
            },
            py::arg("paths"), py::arg("stats") = false)
+      .def("get_many",
+           [](zk::ZkClient& c, const std::vector<std::string>& paths, bool watch) {
+             std::vector<std::string> datas;
+             std::vector<zk::Stat> sts;
+             std::vector<int> rcs;
+             {
+               py::gil_scoped_release rel;
+               rcs = c.get_many(paths, watch, &datas, &sts);
+             }
+             py::list d, s;
+             for (const auto& x : datas) d.append(py::bytes(x));
+             for (const auto& st : sts) s.append(stat_to_dict(st));
+             return py::make_tuple(rcs, d, s);
+           },
+           py::arg("paths"), py::arg("watch") = false)
       .def("multi",
            [](zk::ZkClient& c, const py::list& ops) {
              std::vector<zk::ZkClient::MixedOp> mops;
@@ -557,6 +602,84 @@ PYBIND11_MODULE(_core, m) {
            })
       .def("session_id", &Orchestrator::session_id)
       .def("expired", &Orchestrator::expired);
+
+  // ---- resolver ----
+  py::class_<Resolver>(m, "Resolver")
+      .def(py::init([](const std::vector<std::pair<std::string, int>>& servers, int session_timeout_ms,
+                       const std::string& local_address, size_t max_domains, int connect_timeout_ms,
+                       bool randomize_start, const std::string& log_level) {
+             ResolverConfig cfg;
+             // a resolver retries its first connect for ever, and quickly: a
+             // binder started before its ensemble is up serves once it is
+             cfg.client = client_config_from_args(servers, session_timeout_ms, connect_timeout_ms, 50, 1000, -1,
+                                                  randomize_start, log_level);
+             cfg.local_address = local_address;
+             cfg.max_domains = max_domains;
+             return std::make_unique<Resolver>(std::move(cfg), make_logger("resolver", log_level));
+           }),
+           py::arg("servers"), py::arg("session_timeout_ms") = 30000, py::arg("local_address") = "",
+           py::arg("max_domains") = 1024, py::arg("connect_timeout_ms") = 4000, py::arg("randomize_start") = true,
+           py::arg("log_level") = "error")
+      .def("start", &Resolver::start, py::call_guard<py::gil_scoped_release>())
+      .def("stop", &Resolver::stop, py::call_guard<py::gil_scoped_release>())
+      .def("lookup",
+           [](Resolver& r, const std::string& domain, int64_t timeout_ms, bool local_first) {
+             ResolverSnapshot snap;
+             LookupStatus st;
+             {
+               py::gil_scoped_release rel;
+               st = r.lookup(domain, timeout_ms, &snap, local_first);
+             }
+             py::dict d = snapshot_to_dict(snap);
+             d["status"] = st == LookupStatus::Ok ? "ok" : st == LookupStatus::Absent ? "absent" : "unavailable";
+             return d;
+           },
+           py::arg("domain"), py::arg("timeout_ms") = 5000, py::arg("local_first") = false)
+      .def("snapshot",
+           [](const Resolver& r, const std::string& domain, bool local_first) {
+             ResolverSnapshot snap;
+             {
+               py::gil_scoped_release rel;
+               snap = r.snapshot(domain, local_first);
+             }
+             return snapshot_to_dict(snap);
+           },
+           py::arg("domain"), py::arg("local_first") = false)
+      .def("watch", &Resolver::watch, py::call_guard<py::gil_scoped_release>())
+      .def("domains", &Resolver::domains, py::call_guard<py::gil_scoped_release>())
+      .def("poll_events",
+           [](Resolver& r) {
+             std::vector<ResolverEvent> evs;
+             {
+               py::gil_scoped_release rel;
+               evs = r.poll_events();
+             }
+             py::list out;
+             for (const auto& ev : evs) {
+               py::dict d;
+               d["type"] = ev.type;
+               d["domain"] = ev.domain;
+               d["name"] = ev.name;
+               d["generation"] = ev.generation;
+               out.append(d);
+             }
+             return out;
+           })
+      .def("session_id", &Resolver::session_id, py::call_guard<py::gil_scoped_release>())
+      .def("connected", &Resolver::connected, py::call_guard<py::gil_scoped_release>())
+      .def("stats", [](const Resolver& r) {
+        ResolverStats st;
+        {
+          py::gil_scoped_release rel;
+          st = r.stats();
+        }
+        py::dict d;
+        d["passes"] = st.passes;
+        d["events_applied"] = st.events_applied;
+        d["direct_reads"] = st.direct_reads;
+        d["resyncs_after_expiry"] = st.resyncs_after_expiry;
+        return d;
+      });
 
   // ---- GPU topology ----
   m.def("gpu_count", &gpu::gpu_count);

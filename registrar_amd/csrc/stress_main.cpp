@@ -19,7 +19,11 @@
 //     threads, one TreeLock, one plain counter,
 //   - then a quorum phase on a 3-server quorum-mode ensemble of its own (see
 //     quorum_phase): registered clients heartbeat while the chaos thread
-//     crosses the majority boundary in both directions.
+//     crosses the majority boundary in both directions,
+//   - then a resolver phase on a 3-server ensemble of its own (see
+//     resolver_phase): one Resolver keeps a view of a domain that several
+//     sessions register and unregister under, while servers die and return
+//     and the resolver's own session is expired.
 // At the end, with every client closed and every session gone, the tree must
 // pass Ensemble::audit() and hold no ephemeral.
 // Exit code 0 = every cycle behaved and the end state is sound; sanitizers
@@ -30,6 +34,7 @@
 #include <sys/syscall.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -40,6 +45,7 @@
 #include "ensemble.hpp"
 #include "node_store.hpp"
 #include "registrar.hpp"
+#include "resolver.hpp"
 #include "zkclient.hpp"
 
 using namespace registrar;
@@ -429,6 +435,182 @@ bool quorum_phase(int nclients, int seconds, const Logger& log) {
          total == static_cast<size_t>(nclients) * 21 && eph == total && qs.losses == crossings.load() &&
          crossings.load() > 0 && heartbeats.load() > 0;
 }
+
+// Resolver phase, on a 3-server ensemble of its own. `nclients` sessions create,
+// rewrite and delete ephemeral host records under one domain (neighbouring
+// sessions share some names), a chaos thread kills and restarts servers,
+// always leaving one up, the resolver's own session is expired once half way,
+// and a reader thread takes snapshots all the while: generation must never
+// fall, hosts must be sorted and unique (local ones first when asked so), and
+// no host may have an empty payload. At the end, with the writers quiet, their
+// sessions still open and every server back, the view must equal the tree,
+// name for name and byte for byte, and audit() must be empty.
+bool resolver_phase(int nclients, int seconds, const Logger& log) {
+  zk::EnsembleConfig ecfg;
+  ecfg.ports = {0, 0, 0};
+  ecfg.tick_ms = 50;
+  ecfg.min_session_timeout_ms = 300;
+  ecfg.log_level = LogLevel::Error;
+  zk::Ensemble ens(ecfg);
+  ens.start();
+  std::vector<int> ports = ens.ports();
+  auto client_cfg = [&] {
+    zk::ZkClientConfig ccfg;
+    for (int p : ports) ccfg.servers.push_back({"127.0.0.1", p});
+    ccfg.session_timeout_ms = 4000;
+    ccfg.connect_timeout_ms = 1000;
+    ccfg.connect_initial_delay_ms = 20;
+    ccfg.connect_max_delay_ms = 100;
+    ccfg.log_level = LogLevel::Fatal;
+    return ccfg;
+  };
+  const std::string domain = "res.stress.test";
+  const std::string path = domain_to_path(domain);
+  {
+    zk::ZkClient setup(client_cfg(), log);
+    setup.start();
+    if (!setup.wait_connected(5000) || setup.mkdirp(path) != zk::kZOk) return false;
+    setup.put(path, R"({"type":"service","service":{"type":"service","service":{"srvce":"_s","proto":"_tcp","port":80}}})");
+    setup.close();
+  }
+
+  ResolverConfig rcfg;
+  rcfg.client = client_cfg();
+  rcfg.local_address = "10.0.0.1";
+  Resolver resolver(rcfg, log);
+  resolver.start();
+  ResolverSnapshot first;
+  if (resolver.lookup(domain, 10000, &first) != LookupStatus::Ok) return false;
+
+  std::atomic<bool> stop{false};
+  std::atomic<uint64_t> writes{0}, snapshots{0}, bad{0};
+  std::vector<std::unique_ptr<zk::ZkClient>> held(static_cast<size_t>(nclients));
+  auto writer_fn = [&](int idx) {
+    uint64_t rng = 0x9E3779B97F4A7C15ull * static_cast<uint64_t>(idx + 1);
+    auto next = [&rng] {
+      rng ^= rng << 13;
+      rng ^= rng >> 7;
+      rng ^= rng << 17;
+      return rng;
+    };
+    std::unique_ptr<zk::ZkClient>& client = held[static_cast<size_t>(idx)];
+    while (!stop.load()) {
+      if (!client || client->state() == zk::SessionState::Expired || client->state() == zk::SessionState::Closed) {
+        if (client) client->close();
+        client = std::make_unique<zk::ZkClient>(client_cfg(), log);
+        client->start();
+      }
+      if (!client->wait_connected(200)) continue;
+      // six names per writer, two of them shared with the next writer
+      int slot = (idx * 4 + static_cast<int>(next() % 6)) % (nclients * 4);
+      std::string node = path + "/h" + std::to_string(slot);
+      std::string rec = "{\"type\":\"host\",\"address\":\"10.0.0." + std::to_string(next() % 4) +
+                        "\",\"host\":{\"seq\":" + std::to_string(next() % 1000000) + "}}";
+      switch (next() % 3) {
+        case 0:
+          client->create(node, rec, zk::kEphemeral);
+          break;
+        case 1:
+          client->set(node, rec, -1);
+          break;
+        default:
+          client->del(node, -1);
+          break;
+      }
+      writes.fetch_add(1);
+      std::this_thread::sleep_for(std::chrono::microseconds(200 + next() % 800));
+    }
+  };
+  auto reader_fn = [&] {
+    uint64_t last = 0;
+    bool local_first = false;
+    while (!stop.load()) {
+      ResolverSnapshot s = resolver.snapshot(domain, local_first);
+      if (!s.exists || !s.synced || s.generation < last) bad.fetch_add(1);
+      last = s.generation;
+      for (size_t i = 0; i < s.hosts.size(); i++) {
+        const ResolvedHost& h = s.hosts[i];
+        if (h.payload.empty() || !h.has_address || h.ports != std::vector<int64_t>{80}) bad.fetch_add(1);
+        if (h.local != (h.address == "10.0.0.1")) bad.fetch_add(1);
+        if (i == 0) continue;
+        const ResolvedHost& p = s.hosts[i - 1];
+        bool ordered = local_first ? (p.local != h.local ? p.local : p.name < h.name) : p.name < h.name;
+        if (!ordered) bad.fetch_add(1);
+      }
+      resolver.poll_events();  // an observer that keeps up
+      local_first = !local_first;
+      snapshots.fetch_add(1);
+      std::this_thread::sleep_for(std::chrono::microseconds(100));
+    }
+  };
+  auto chaos_fn = [&] {
+    size_t victim = 0;
+    while (!stop.load()) {
+      std::this_thread::sleep_for(std::chrono::milliseconds(200));
+      ens.kill_server(victim);
+      std::this_thread::sleep_for(std::chrono::milliseconds(150));
+      ens.restart_server(victim);
+      victim = (victim + 1) % 3;
+    }
+    for (size_t i = 0; i < 3; i++)
+      if (!ens.server_up(i)) ens.restart_server(i);
+  };
+
+  std::vector<std::thread> threads;
+  for (int i = 0; i < nclients; i++) threads.emplace_back(writer_fn, i);
+  std::thread reader(reader_fn), chaos(chaos_fn);
+  std::this_thread::sleep_for(std::chrono::milliseconds(seconds * 500));
+  int64_t old_session = resolver.session_id();
+  ens.expire_session(old_session);
+  std::this_thread::sleep_for(std::chrono::milliseconds(seconds * 500));
+  stop.store(true);
+  for (auto& t : threads) t.join();
+  reader.join();
+  chaos.join();
+
+  // everything is quiet: the writers' sessions are still open, so the tree
+  // holds whatever they created last. The view has to get there by itself.
+  auto matches = [&] {
+    ResolverSnapshot s = resolver.snapshot(domain);
+    std::vector<std::string> names = ens.children(path);
+    std::sort(names.begin(), names.end());
+    if (s.stale || !s.synced || s.hosts.size() != names.size()) return false;
+    for (size_t i = 0; i < names.size(); i++)
+      if (s.hosts[i].name != names[i] || s.hosts[i].payload != ens.get(path + "/" + names[i]).data) return false;
+    return true;
+  };
+  auto deadline = std::chrono::steady_clock::now() + std::chrono::seconds(20);
+  bool equal = false;
+  while (!(equal = matches()) && std::chrono::steady_clock::now() < deadline)
+    std::this_thread::sleep_for(std::chrono::milliseconds(20));
+  ResolverStats rs = resolver.stats();
+  ResolverSnapshot last = resolver.snapshot(domain);
+  bool new_session = resolver.session_id() != old_session && resolver.session_id() != 0;
+  // a writer that replaced an expired session shortly before the end may
+  // still have that session's drain in flight; a real violation stays
+  std::vector<std::string> violations = ens.audit();
+  deadline = std::chrono::steady_clock::now() + std::chrono::seconds(2);
+  while (!violations.empty() && std::chrono::steady_clock::now() < deadline) {
+    std::this_thread::sleep_for(std::chrono::milliseconds(20));
+    violations = ens.audit();
+  }
+  resolver.stop();
+  for (auto& c : held)
+    if (c) c->close();
+  ens.stop();
+
+  printf("stress: resolver phase: %llu writes by %d sessions, %llu snapshots, %llu passes, %llu changes applied, "
+         "%llu resyncs after expiry, %zu hosts at generation %llu, %llu unexpected\n",
+         static_cast<unsigned long long>(writes.load()), nclients, static_cast<unsigned long long>(snapshots.load()),
+         static_cast<unsigned long long>(rs.passes), static_cast<unsigned long long>(rs.events_applied),
+         static_cast<unsigned long long>(rs.resyncs_after_expiry), last.hosts.size(),
+         static_cast<unsigned long long>(last.generation), static_cast<unsigned long long>(bad.load()));
+  for (const auto& v : violations) printf("stress: resolver phase: audit: %s\n", v.c_str());
+  if (!equal) printf("stress: resolver phase: the view did not converge to the tree\n");
+  if (!new_session) printf("stress: resolver phase: the resolver did not get a new session after its expiry\n");
+  return equal && new_session && violations.empty() && bad.load() == 0 && rs.resyncs_after_expiry >= 1 &&
+         rs.events_applied > 0 && writes.load() > 0 && snapshots.load() > 0;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -591,6 +773,7 @@ int main(int argc, char** argv) {
   bool crossed_ok = crossed_secs <= 0 || crossed_phase(crossed_secs, log);
   bool treelock_ok = treelock_phase();
   bool quorum_ok = seconds <= 0 || quorum_phase(nclients, std::max(3, seconds / 2), log);
+  bool resolver_ok = seconds <= 0 || resolver_phase(nclients, std::max(3, seconds / 2), log);
 
   // End state. Every client is closed, so every session ends: by its close,
   // or (where the close was lost to a killed server) by the expiry sweep. A
@@ -637,5 +820,6 @@ int main(int argc, char** argv) {
   if (!crossed_ok) printf("stress: the crossed-parents phase failed\n");
   if (!treelock_ok) printf("stress: the tree lock phase failed\n");
   if (!quorum_ok) printf("stress: the quorum phase failed\n");
-  return (behaved && sound && crossed_ok && treelock_ok && quorum_ok) ? 0 : 1;
+  if (!resolver_ok) printf("stress: the resolver phase failed\n");
+  return (behaved && sound && crossed_ok && treelock_ok && quorum_ok && resolver_ok) ? 0 : 1;
 }

@@ -505,7 +505,7 @@ struct ZkClient::Impl {
             exist_watch_paths.erase(ev.path);
             break;
         }
-        {
+        if (cfg.queue_watches) {
           std::lock_guard<std::mutex> g(watch_mu);
           watch_queue.push_back(ev);
         }
@@ -898,6 +898,80 @@ void ZkClient::achildren(const std::string& path, bool watch, ChildrenCallback c
                        if (cb) cb(rc, children);
                      });
   });
+}
+
+namespace {
+// One get_many in flight: shared by its N per-request completions, which all
+// run on the loop thread.
+struct GetManyState {
+  std::vector<std::string> paths;
+  std::vector<int> rcs;
+  std::vector<std::string> datas;
+  std::vector<Stat> stats;
+  size_t left = 0;
+  int lost = kZOk;  // the connection or session error that ended the batch
+  ZkClient::DataManyCallback cb;
+};
+}  // namespace
+
+void ZkClient::aget_many(std::vector<std::string> paths, bool watch, DataManyCallback cb) {
+  auto st = std::make_shared<GetManyState>();
+  st->paths = std::move(paths);
+  size_t n = st->paths.size();
+  st->rcs.assign(n, kZConnectionLoss);
+  st->datas.assign(n, std::string());
+  st->stats.assign(n, Stat{});
+  st->left = n;
+  st->cb = std::move(cb);
+  impl_->loop.post([this, st, watch, n] {
+    if (n == 0) {
+      if (st->cb) st->cb(st->rcs, st->datas, st->stats);
+      return;
+    }
+    Impl* impl = impl_.get();
+    for (size_t i = 0; i < n; i++) {
+      const std::string& path = st->paths[i];
+      impl->submit_op(kOpGetData,
+                      [&path, watch](JuteWriter& w) {
+                        w.write_string(path);
+                        w.write_bool(watch);
+                      },
+                      [st, impl, watch, i](int rc, JuteReader* r) {
+                        // decode first: a body that throws leaves no trace, and
+                        // handle_frame then calls again with kZConnectionLoss
+                        if (rc == kZOk && r) {
+                          GetDataResponse resp;
+                          resp.deserialize(*r);
+                          st->datas[i] = std::move(resp.data);
+                          st->stats[i] = resp.stat;
+                        }
+                        if (watch && rc == kZOk) impl->data_watch_paths.insert(st->paths[i]);
+                        st->rcs[i] = rc;
+                        if ((rc == kZConnectionLoss || rc == kZSessionExpired) && st->lost == kZOk) st->lost = rc;
+                        if (--st->left != 0) return;
+                        if (st->lost != kZOk) {
+                          st->rcs.assign(st->rcs.size(), st->lost);
+                          st->datas.assign(st->datas.size(), std::string());
+                          st->stats.assign(st->stats.size(), Stat{});
+                        }
+                        if (st->cb) st->cb(st->rcs, st->datas, st->stats);
+                      });
+    }
+  });
+}
+
+std::vector<int> ZkClient::get_many(const std::vector<std::string>& paths, bool watch,
+                                    std::vector<std::string>* datas, std::vector<Stat>* stats) {
+  if (datas) datas->assign(paths.size(), std::string());
+  if (stats) stats->assign(paths.size(), Stat{});
+  if (paths.empty()) return {};
+  std::promise<std::vector<int>> p;
+  aget_many(paths, watch, [&](std::vector<int>& rcs, std::vector<std::string>& d, std::vector<Stat>& s) {
+    if (datas) *datas = std::move(d);
+    if (stats) *stats = std::move(s);
+    p.set_value(std::move(rcs));
+  });
+  return p.get_future().get();
 }
 
 // ---- sync wrappers ----

@@ -68,6 +68,10 @@ struct ZkClientConfig {
   // start at a random server (ZK-client convention; set false when the
   // caller pre-ordered the list for deterministic load balance)
   bool randomize_start = true;
+  // keep every watch event for poll_watches(). An owner that consumes events
+  // through the watch callback alone turns this off: nothing drains the queue
+  // then, and it would grow by one entry per event for the life of the client.
+  bool queue_watches = true;
   LogLevel log_level = LogLevel::Warn;
 };
 
@@ -90,6 +94,10 @@ class ZkClient {
   using VoidCallback = std::function<void(int rc)>;
   using DataCallback = std::function<void(int rc, const std::string& data, const Stat& stat)>;
   using ChildrenCallback = std::function<void(int rc, const std::vector<std::string>& children)>;
+  // get_many: rcs, datas and stats in the order of the paths. The vectors are
+  // the callback's to keep (move from them freely).
+  using DataManyCallback =
+      std::function<void(std::vector<int>& rcs, std::vector<std::string>& datas, std::vector<Stat>& stats)>;
   using EventCallback = std::function<void(const SessionEvent&)>;
   using WatchCallback = std::function<void(const WatcherEvent&)>;
 
@@ -127,6 +135,13 @@ class ZkClient {
   void aget(const std::string& path, bool watch, DataCallback cb);
   void aset(const std::string& path, const std::string& data, int32_t version, StatCallback cb);
   void achildren(const std::string& path, bool watch, ChildrenCallback cb);
+  // N getData requests in one submission, completed as a unit: cb runs once,
+  // after the last reply. With watch=true every path answered kZOk joins the
+  // data watches, as aget(path, true) would; kZNoNode arms nothing. Reads are
+  // all-or-nothing towards the caller: if the connection (or the session) is
+  // lost before the last reply, or a body does not decode, every rc of the
+  // batch is that error, the earlier answers included.
+  void aget_many(std::vector<std::string> paths, bool watch, DataManyCallback cb);
 
   // ---- sync ops (any thread but the loop thread) ----
   // watch=true registers a one-shot watch on the path (delivered through the
@@ -155,6 +170,9 @@ class ZkClient {
                                int32_t flags);
   std::vector<int> delete_many(const std::vector<std::string>& paths);
   std::vector<int> exists_many(const std::vector<std::string>& paths, std::vector<Stat>* stats = nullptr);
+  // blocking aget_many
+  std::vector<int> get_many(const std::vector<std::string>& paths, bool watch,
+                            std::vector<std::string>* datas = nullptr, std::vector<Stat>* stats = nullptr);
 
   // Heterogeneous pipelined batch (delete/create mixes). ZooKeeper processes
   // a session's requests strictly in order, so a stage sequence whose only

@@ -22,6 +22,7 @@ ext = Pybind11Extension(
         os.path.join(CSRC, "health.cpp"),
         os.path.join(CSRC, "orchestrator.cpp"),
         os.path.join(CSRC, "gpu.cpp"),
+        os.path.join(CSRC, "resolver.cpp"),
     ],
     # a header edit must rebuild every TU (setuptools skips unchanged .cpp
     # otherwise — a jute.hpp fix once shipped stale objects)
